@@ -11,9 +11,19 @@
 A step = one pass of the hot path (VAE encode -> UNet @ t=999 -> DDPM step -> VAE decode with skips) over one batch
 of synthetic inputs already resident in HBM, replayed as a hipGraph; for N > 1 each rank runs its own batch shard
 (weak scaling, weights replicated, no data-path collective) and the finished images are gathered to rank 0 over RCCL
-inside the timed region.  Rank 0 prints ONE JSON line.  At N = 1 the line also carries the roofline of the dominant
-kernel (HIP events on the launch stream), the bs=1 latency, the CPU oracle timed on image 0 of the SAME inputs, and
-the parity of the GPU output against that oracle image (``parity_max_abs`` / ``parity_psnr_db``).
+inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times --steps steps and prints the headline line (``value``, ``ms_per_step``).
+``--full`` adds everything else, measured after the timed region: at N = 1 the roofline of the dominant kernel (HIP
+events on the launch stream), the box calibration, power and clock, the bs=1 / 8 / 32 latencies, the exact-f32 and
+fp16 precision modes, the CPU oracle timed on image 0 of the SAME inputs and the parity of the GPU output against that
+oracle image (``parity_max_abs`` / ``parity_psnr_db``); at N > 1 the per-rank compute time without the gather.
+
+    python bench.py --steps 20 --warmup 5 --dump-outputs DIR    # + DIR/images.npy: the last timed step's images, float32
+
+``--dump-outputs`` writes what the timed path computed in its last step (the images a caller receives; rank 0's gathered
+batch for N > 1) as float32 ``.npy`` files; an output past DUMP_MAX_BYTES is written as ``<name>_sample.npy``, a fixed
+seeded sample of its elements.  Weights and inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -33,11 +43,12 @@ if ROOT not in sys.path:
 F_ALG = {512: 4.477e12, 1024: 20.22e12}   # algorithmic FLOP / image
 PEAK_TF = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}   # dense MFMA peaks, MI355X_MICROARCH.md
 CPU_BASELINE_THREADS = 16
-CPU_BASELINE_TIMED = 2        # + 1 warm-up: ~30 s of CPU work in the default run
+CPU_BASELINE_TIMED = 2        # + 1 warm-up: ~30 s of CPU work in the --full run
 PER_OP_PATH = None
 DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 TRAFFIC_JSON = os.path.join(ROOT, "profiles", "traffic_conv3x3.json")   # tools/pmc_traffic.py, PMC passes of THIS command (every conv3x3_* launch)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E spec peak (6.3 TB/s achievable)
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: all files together stay under 64 MB
 
 
 def synth_inputs(kind, B, size, cross_dim, lat, seed):
@@ -55,6 +66,24 @@ def synth_inputs(kind, B, size, cross_dim, lat, seed):
     eps = torch.randn(B, lat, size // 8, size // 8, generator=g)
     noise = torch.randn(B, lat, size // 8, size // 8, generator=g)
     return x, cap, eps, noise
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every tensor of ``arrays`` as DIR/<name>.npy in float32.  One past its share of DUMP_MAX_BYTES is written
+    as DIR/<name>_sample.npy instead: the elements of the flattened tensor at a fixed, seeded set of indices, in index order."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    limit = DUMP_MAX_BYTES // 4 // max(1, len(arrays))     # float32 elements per tensor
+    written = []
+    for name, t in arrays.items():
+        t = t.detach().float().cpu().contiguous()
+        if t.numel() > limit:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:limit].sort().values
+            t, name = t.reshape(-1)[idx], name + "_sample"
+        path = os.path.join(d, name + ".npy")
+        np.save(path, t.numpy())
+        written.append("%s %s" % (os.path.basename(path), list(t.shape)))
+    print("bench.py: outputs of the last timed step written to %s: %s" % (d, ", ".join(written)), file=sys.stderr, flush=True)
 
 
 def source_hash():
@@ -378,6 +407,12 @@ def main():
     ap.add_argument("--direction", default="a2b", choices=["a2b", "b2a"], help="CycleGAN direction (day_to_night = a2b)")
     ap.add_argument("--stochastic", action="store_true", help="sketch_to_image_stochastic path: TwinConv, noise interpolation, r-scaled LoRA/skips")
     ap.add_argument("--gamma", type=float, default=0.4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure everything beyond the headline figure (roofline, calibration, power, latencies, "
+                         "other precisions, CPU oracle and parity at N = 1; per-rank compute time at N > 1); the --no-* and --per-op options "
+                         "below trim this part")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the images of the last timed step as DIR/<name>.npy (float32; a fixed seeded sample past %d MiB)" % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-f32", action="store_true", help="skip the exact-f32-mode replays (images_per_s_f32 / parity_max_abs_f32) of the N = 1 line")
@@ -395,6 +430,10 @@ def main():
                          "(what real SD-VAE activations do; the 1/sqrt(fan_in) synthetic weights keep everything zero-mean), GroupNorm groups trip the "
                          "cancellation test and take the second, shifted pass (csrc/norm.hip gn_refine_group) -- prices that path in the step")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.per_op and not a.full:
+        ap.error("--per-op is part of the --full measurements")
     global PER_OP_PATH
     PER_OP_PATH = a.per_op
     if a.batch is None:
@@ -507,8 +546,13 @@ def main():
     elapsed = dp.max_over_ranks(time.perf_counter() - t0, dev)
     ms_per_step = elapsed / a.steps * 1e3
     value = total * a.steps / elapsed
+    mark("warmup_and_timed_region")
+    if a.dump_outputs and rank == 0:
+        # before anything else replays the graph: plan.out (or the gathered batch) is still the last timed step's
+        dump_outputs(a.dump_outputs, {"images": gather.images() if gather is not None else plan.out})
+        mark("dump_outputs")
     ms_compute = None
-    if world > 1:
+    if world > 1 and a.full:
         # attribution of a scaling shortfall (outside the timed region): the same steps without the gather, per rank
         dp.barrier()
         torch.cuda.synchronize()
@@ -518,7 +562,6 @@ def main():
         torch.cuda.synchronize()
         ms_compute = [round(v / a.steps * 1e3, 3) for v in dp.all_ranks(time.perf_counter() - t1, dev)]
 
-    mark("warmup_and_timed_region")
     if rank != 0:
         return
     name = {"pix2pix": "pix2pix-turbo sketch_to_image_stochastic gamma=%g" % a.gamma if a.stochastic else "pix2pix-turbo edge_to_image",
@@ -535,8 +578,9 @@ def main():
     if a.activation_offset:
         rec["config"]["activation_offset"] = a.activation_offset
     if world > 1:
-        rec["ms_compute_per_rank"] = ms_compute                     # replay only (no gather), measured after the timed region
-        rec["ms_gather"] = round(ms_per_step - max(ms_compute), 3)   # what the RCCL gather adds to the slowest rank's step
+        if ms_compute is not None:
+            rec["ms_compute_per_rank"] = ms_compute                     # replay only (no gather), measured after the timed region
+            rec["ms_gather"] = round(ms_per_step - max(ms_compute), 3)   # what the RCCL gather adds to the slowest rank's step
         rec["gather"] = "serial (launch stream waits)" if a.serial_gather else "double-buffered, overlapped with the next replay (side stream)"
         rec["setup_s_per_rank"] = [round(v, 1) for v in setup_s]      # weights (built once on rank 0, mapped by the others) + packed + uploaded + plan
         rec["weights_s_rank0"] = round(t_weights, 1)
@@ -545,7 +589,7 @@ def main():
         rec["e2e_mfma_frac"] = round(value / world * falg / 1e12 / PEAK_TF[a.dtype], 4)
     if emu:
         rec["data"] = "EMULATED on the CPU (test hook): " + rec["data"]
-    if world == 1 and not emu:
+    if world == 1 and not emu and a.full:
         roof, breakdown, tot = kernel_roofline(plan, a.dtype)
         rec["roofline"] = roof
         rec["kernel_breakdown_ms"] = breakdown

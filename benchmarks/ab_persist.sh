@@ -10,4 +10,4 @@ for w in 0 default; do
 done
 unset I2I_PERSIST_WGS
 echo "== bench default" >> $O
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline >> $O 2>&1
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline >> $O 2>&1

@@ -3,7 +3,7 @@
 # conv (csrc/build.py --tag trace --defs=-DI2I_TRACE=1), one PMC pass over the attention kernels, and where the GPU test
 # suite spends its wall time ([phase] lines of tests/test_e2e_gpu.py).
 O=gpurun_out; mkdir -p $O; export TMPDIR=/tmp
-python bench.py --per-op $O/r5a_per_op_bs8.txt --no-cpu-baseline > $O/r5a_bench_bs8.json 2> $O/r5a_bench_bs8.err
+python bench.py --full --per-op $O/r5a_per_op_bs8.txt --no-cpu-baseline > $O/r5a_bench_bs8.json 2> $O/r5a_bench_bs8.err
 LIBT=img2img-turbo_amd/csrc/libi2i_turbo_trace.so
 if [ -f $LIBT ]; then
   for extra in "" "--res"; do

@@ -14,9 +14,9 @@ for rep in 1 2; do
   done
 done > $O/r5b_w32_ab.log 2>&1
 grep -v amdgpu.ids $O/r5b_w32_ab.log
-python bench.py --no-cpu-baseline --no-f32 --per-op $O/r5b_per_op_bs8.txt > $O/r5b_bench_bs8.json 2> $O/r5b_bench_bs8.err
+python bench.py --full --no-cpu-baseline --no-f32 --per-op $O/r5b_per_op_bs8.txt > $O/r5b_bench_bs8.json 2> $O/r5b_bench_bs8.err
 cut -c1-400 $O/r5b_bench_bs8.json
-I2I_LIB=$OLD python bench.py --no-cpu-baseline --no-f32 --no-latency > $O/r5b_bench_bs8_r4lib.json 2>> $O/r5b_bench_bs8.err
+I2I_LIB=$OLD python bench.py --full --no-cpu-baseline --no-f32 --no-latency > $O/r5b_bench_bs8_r4lib.json 2>> $O/r5b_bench_bs8.err
 cut -c1-400 $O/r5b_bench_bs8_r4lib.json
 timeout 300 python -m pytest tests/test_e2e_gpu.py -m gpu -x -q -k "cfg2 or tiny_pix2pix" > $O/r5b_tests_e2e.log 2>&1
 tail -3 $O/r5b_tests_e2e.log

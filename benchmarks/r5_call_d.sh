@@ -12,7 +12,7 @@ for fill in randn const zero; do
   echo "== fill $fill"
   python benchmarks/bench_ops.py --tiles 0 --iters 5 --fill $fill --only "vae 128->128@512 gn,vae 512->512@128 gn,unet lin 1280->10240 T256" --out $O/r5d_ops.json
 done 2>&1 | grep -v amdgpu.ids | tee $O/r5d_fill.log
-python bench.py --no-cpu-baseline --per-op $O/r5d_per_op_bs8.txt > $O/r5d_bench_bs8.json 2> $O/r5d_bench_bs8.err
+python bench.py --full --no-cpu-baseline --per-op $O/r5d_per_op_bs8.txt > $O/r5d_bench_bs8.json 2> $O/r5d_bench_bs8.err
 cut -c1-300 $O/r5d_bench_bs8.json; python - <<'PY'
 import json
 r=json.load(open('gpurun_out/r5d_bench_bs8.json'))

@@ -15,8 +15,8 @@ SH="unet 320->320@64 gn,unet 960->320@64 gn,unet 640->640@32 gn,unet 1280->640@3
 for rep in 1 2; do for lib in $OLD $NEW; do echo "== $lib rep $rep"; python benchmarks/bench_ops.py --lib $lib --nogn --tiles 51,53 --iters 5 --only "$SH" --out $O/r5g_ops.json; done; done 2>&1 | grep -v "amdgpu.ids\|n/a" | tee $O/r5g_gather_order_ab.log
 timeout 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/r5g_fetch -o fetch -- python benchmarks/bench_ops.py --nogn --tiles 51 --iters 3 --only "unet 960->320@64 gn" --out $O/r5g_ops.json > /dev/null 2>&1
 python tools/pmc_summary.py $(find $O/r5g_fetch -name "*counter_collection.csv" | head -1) gemm_w32_kernel 2>&1 | tee $O/r5g_pmc_gather_fetch.txt
-I2I_LIB=$OLD python bench.py --no-cpu-baseline --no-f32 --no-latency > $O/r5g_bench_bs8_oldlib.json 2> $O/r5g_bench_bs8.err
-python bench.py --no-cpu-baseline --no-f32 --per-op $O/r5g_per_op_bs8.txt > $O/r5g_bench_bs8.json 2>> $O/r5g_bench_bs8.err
+I2I_LIB=$OLD python bench.py --full --no-cpu-baseline --no-f32 --no-latency > $O/r5g_bench_bs8_oldlib.json 2> $O/r5g_bench_bs8.err
+python bench.py --full --no-cpu-baseline --no-f32 --per-op $O/r5g_per_op_bs8.txt > $O/r5g_bench_bs8.json 2>> $O/r5g_bench_bs8.err
 python - <<'PY'
 import json
 r=json.load(open('gpurun_out/r5g_bench_bs8.json'))

@@ -26,12 +26,12 @@ for rep in 1 2; do
   done
 done 2>&1 | grep -v "amdgpu.ids\|n/a" | tee $O/r5i_g32_epilogue_ab.log
 for rep in 1 2; do
-I2I_LIB=$OLD python bench.py --no-cpu-baseline --no-f32 --no-power --no-latency > $O/r5i_bench_bs8_old_$rep.json 2>> $O/r5i_bench.err
-python bench.py --no-cpu-baseline --no-f32 --no-power --no-latency > $O/r5i_bench_bs8_new_$rep.json 2>> $O/r5i_bench.err
+I2I_LIB=$OLD python bench.py --full --no-cpu-baseline --no-f32 --no-power --no-latency > $O/r5i_bench_bs8_old_$rep.json 2>> $O/r5i_bench.err
+python bench.py --full --no-cpu-baseline --no-f32 --no-power --no-latency > $O/r5i_bench_bs8_new_$rep.json 2>> $O/r5i_bench.err
 done
-I2I_LIB=$OLD python bench.py --batch 1 --no-cpu-baseline --no-f32 --no-power > $O/r5i_bench_bs1_old.json 2>> $O/r5i_bench.err
-python bench.py --batch 1 --no-cpu-baseline --no-f32 --no-power > $O/r5i_bench_bs1_new.json 2>> $O/r5i_bench.err
-python bench.py --no-cpu-baseline --no-f32 --per-op $O/r5i_per_op_bs8.txt > $O/r5i_bench_bs8.json 2>> $O/r5i_bench.err
+I2I_LIB=$OLD python bench.py --full --batch 1 --no-cpu-baseline --no-f32 --no-power > $O/r5i_bench_bs1_old.json 2>> $O/r5i_bench.err
+python bench.py --full --batch 1 --no-cpu-baseline --no-f32 --no-power > $O/r5i_bench_bs1_new.json 2>> $O/r5i_bench.err
+python bench.py --full --no-cpu-baseline --no-f32 --per-op $O/r5i_per_op_bs8.txt > $O/r5i_bench_bs8.json 2>> $O/r5i_bench.err
 python - <<'PY'
 import json
 for n in ("bs8_old_1","bs8_new_1","bs8_old_2","bs8_new_2","bs1_old","bs1_new","bs8"):

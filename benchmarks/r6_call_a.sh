@@ -2,9 +2,9 @@
 # Round-6 baseline on the tree of the round start: the headline line, per-op tables at batch 8 and batch 1 (which launches the
 # UNet-side work of the round has to remove), kernel-trace stats of the batch-1 forward.
 O=gpurun_out; T=r6a; export TMPDIR=/tmp; mkdir -p $O
-python bench.py --steps 20 --warmup 5 --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
-python bench.py --batch 1 --no-cpu-baseline --no-f32 --per-op $O/${T}_per_op_bs1.txt > $O/${T}_bench_bs1.json 2>> $O/${T}_bench.err
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_trace_bs1 -o trace -- python bench.py --batch 1 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --no-f32 --no-power > /dev/null 2> $O/${T}_trace_bs1.err
+python bench.py --full --steps 20 --warmup 5 --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
+python bench.py --full --batch 1 --no-cpu-baseline --no-f32 --per-op $O/${T}_per_op_bs1.txt > $O/${T}_bench_bs1.json 2>> $O/${T}_bench.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_trace_bs1 -o trace -- python bench.py --full --batch 1 --steps 20 --warmup 3 --no-cpu-baseline --no-latency --no-f32 --no-power > /dev/null 2> $O/${T}_trace_bs1.err
 cp $(find $O/${T}_trace_bs1 -name "*kernel_stats.csv" | head -1) $O/${T}_bench_bs1_kernel_stats.csv
 rm -rf $O/${T}_trace_bs1
 amd-smi static -g 0 --json > $O/${T}_amd_smi_static.json 2>&1

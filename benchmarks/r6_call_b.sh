@@ -8,8 +8,8 @@ timeout 1500 python -m pytest tests/test_e2e_gpu.py -x -q -m gpu 2>&1 | tail -25
 cat $O/${T}_e2e_tests.log
 python benchmarks/ab.py --arms "I2I_LN_FOLD=0,I2I_GN_NORM=0" "I2I_LN_FOLD=1,I2I_GN_NORM=0" "I2I_LN_FOLD=0,I2I_GN_NORM=1" "I2I_LN_FOLD=1,I2I_GN_NORM=1" --repeats 6 --steps 10 --batch 8 --out $O/${T}_ab_bs8.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs8.log
 python benchmarks/ab.py --arms "I2I_LN_FOLD=0,I2I_GN_NORM=0" "I2I_LN_FOLD=1,I2I_GN_NORM=0" "I2I_LN_FOLD=0,I2I_GN_NORM=1" "I2I_LN_FOLD=1,I2I_GN_NORM=1" --repeats 6 --steps 30 --batch 1 --out $O/${T}_ab_bs1.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs1.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
-python bench.py --batch 1 --no-cpu-baseline --no-f32 --per-op $O/${T}_per_op_bs1.txt > $O/${T}_bench_bs1.json 2>> $O/${T}_bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
+python bench.py --full --batch 1 --no-cpu-baseline --no-f32 --per-op $O/${T}_per_op_bs1.txt > $O/${T}_bench_bs1.json 2>> $O/${T}_bench.err
 tail -5 $O/${T}_bench.err
 for f in $O/${T}_bench_bs8.json $O/${T}_bench_bs1.json; do python - "$f" <<'PY'
 import json, sys

@@ -7,9 +7,9 @@ cat $O/${T}_new_op_tests.log
 ARMS='I2I_W32_UNSPLIT_ROWS=0 I2I_W32_UNSPLIT_ROWS=64 I2I_W32_UNSPLIT_ROWS=256 I2I_W32_UNSPLIT_ROWS=1024 I2I_W32_UNSPLIT_ROWS=4096'
 python benchmarks/ab.py --arms $ARMS --repeats 6 --steps 30 --batch 1 --out $O/${T}_ab_bs1.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs1_unsplit.log
 python benchmarks/ab.py --arms I2I_W32_UNSPLIT_ROWS=0 I2I_W32_UNSPLIT_ROWS=512 I2I_W32_UNSPLIT_ROWS=2048 --repeats 6 --steps 10 --batch 8 --out $O/${T}_ab_bs8.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs8_unsplit.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --no-modes --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
-I2I_W32_UNSPLIT_ROWS=1024 python bench.py --batch 1 --no-cpu-baseline --no-f32 --no-modes --per-op $O/${T}_per_op_bs1_unsplit1024.txt > $O/${T}_bench_bs1_unsplit1024.json 2>> $O/${T}_bench.err
-python bench.py --batch 1 --no-cpu-baseline --no-f32 --no-modes --per-op $O/${T}_per_op_bs1.txt > $O/${T}_bench_bs1.json 2>> $O/${T}_bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --no-modes --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
+I2I_W32_UNSPLIT_ROWS=1024 python bench.py --full --batch 1 --no-cpu-baseline --no-f32 --no-modes --per-op $O/${T}_per_op_bs1_unsplit1024.txt > $O/${T}_bench_bs1_unsplit1024.json 2>> $O/${T}_bench.err
+python bench.py --full --batch 1 --no-cpu-baseline --no-f32 --no-modes --per-op $O/${T}_per_op_bs1.txt > $O/${T}_bench_bs1.json 2>> $O/${T}_bench.err
 tail -3 $O/${T}_bench.err
 for f in $O/${T}_bench_bs8.json $O/${T}_bench_bs1.json $O/${T}_bench_bs1_unsplit1024.json; do python - "$f" <<'PY'
 import json, sys

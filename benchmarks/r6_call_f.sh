@@ -6,7 +6,7 @@ timeout 600 python -m pytest tests/test_ops_gpu.py -x -q -m gpu -k "attention" 2
 OLD=img2img-turbo_amd/csrc/libi2i_turbo_oldatt.so
 python benchmarks/ab.py --arms I2I_LIB=$OLD - I2I_ATT_Q_LOG2=0 --repeats 6 --steps 10 --batch 8 --out $O/${T}_ab_bs8.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs8_attention.log
 python benchmarks/ab.py --arms I2I_LIB=$OLD - --repeats 6 --steps 20 --batch 1 --out $O/${T}_ab_bs1.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs1_attention.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --no-latency --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --no-latency --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
 grep -h "sdpa" $O/${T}_per_op_bs8.txt | head -8
 python - <<'PY'
 import json

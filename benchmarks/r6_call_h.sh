@@ -4,7 +4,7 @@ O=gpurun_out; T=r6h; export TMPDIR=/tmp; mkdir -p $O
 timeout 600 python -m pytest tests/test_ops_gpu.py -x -q -m gpu -k "narrow or small_tile or conv3x3 or halo" 2>&1 | tail -6 | tee $O/${T}_op_tests.log
 python benchmarks/ab.py --arms I2I_CONV_NARROW=0 - --repeats 6 --steps 10 --batch 8 --out $O/${T}_ab_bs8.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs8_conv_narrow_in_out.log
 python benchmarks/ab.py --arms I2I_SMALL_TILE_ROWS=0 - I2I_SMALL_TILE_K=1280 --repeats 6 --steps 20 --batch 1 --out $O/${T}_ab_bs1.json 2>&1 | grep -v amdgpu.ids | tee $O/${T}_ab_bs1_small_tile_short_k.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --no-modes --no-latency --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-f32 --no-modes --no-latency --per-op $O/${T}_per_op_bs8.txt > $O/${T}_bench_bs8.json 2> $O/${T}_bench.err
 grep -h "conv_in\|conv_out" $O/${T}_per_op_bs8.txt
 python - <<'PY'
 import json

@@ -5,7 +5,7 @@
 O=gpurun_out; T=${1:-r6}; export TMPDIR=/tmp; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q --durations=8 > $O/${T}_gputests_final_tree.log 2>&1
 tail -14 $O/${T}_gputests_final_tree.log
-CMD="python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-latency --no-f32 --no-modes --no-power"
+CMD="python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-latency --no-f32 --no-modes --no-power"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/${T}_fetch -o fetch -- $CMD > /dev/null 2> $O/${T}_fetch.err
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/${T}_write -o write -- $CMD > /dev/null 2> $O/${T}_write.err
 F=$(find $O/${T}_fetch -name "*counter_collection.csv" | head -1); W=$(find $O/${T}_write -name "*counter_collection.csv" | head -1)

@@ -477,7 +477,7 @@ def test_bench_two_ranks_on_the_emulator(emu_lib, extra=()):
     per-rank compute times, ms_gather >= 0 up to timer noise."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29757", WORLD_SIZE="2")
     env.pop("I2I_EMU_ASYNC", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--batch", "1", "--emulate", emu_lib.path] + list(extra)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--batch", "1", "--full", "--emulate", emu_lib.path] + list(extra)
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(2)]
     outs = [p.communicate(timeout=900) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-2000:] for o in outs]
@@ -492,6 +492,59 @@ def test_bench_two_ranks_on_the_emulator(emu_lib, extra=()):
     assert rec["ms_gather"] > -0.25 * rec["ms_per_step"], rec            # step - compute: >= 0 up to run-to-run noise of two separate loops
     assert ("serial" in rec["gather"]) == bool(extra)
     assert "roofline" not in rec and rec["data"].startswith("EMULATED")
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+@pytest.mark.slow
+def test_bench_plain_line_and_dumped_outputs_on_the_emulator(emu_lib, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, prints the headline line and none of the --full measurements;
+    --dump-outputs writes the last timed step's images as float32, the same on every run with the same arguments."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("I2I_EMU_ASYNC", "WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    recs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+               "--emulate", emu_lib.path, "--dump-outputs", str(tmp_path / run)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1 and rec["higher_is_better"] is True
+        assert rec["unit"] == "images/s" and rec["dtype"] == "f32" and rec["metric"].startswith("512x512 images/sec")
+        assert abs(rec["value"] - 2 * 1e3 / rec["ms_per_step"]) < 1e-2 * rec["value"], "value = batch / ms_per_step"
+        assert not {"roofline", "calib", "power", "cpu_baseline", "parity_max_abs", "precision_modes", "ms_compute_per_rank"} & set(rec), rec
+    a, b = (np.load(tmp_path / run / "images.npy") for run in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (2, 3, 64, 64) and np.isfinite(a).all() and a.std() > 0
+    assert np.array_equal(a, b), "same arguments, same inputs, same outputs"
+    assert sorted(os.listdir(tmp_path / "a")) == ["images.npy"]
+
+
+def test_bench_dump_samples_an_output_past_the_budget(tmp_path, monkeypatch):
+    """An output larger than DUMP_MAX_BYTES is written as a fixed, seeded sample of its elements (in index order) within the budget."""
+    import numpy as np
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    t = torch.arange(10000, dtype=torch.float64).reshape(4, 2500)      # element i holds i: the sample shows which elements it took
+    bench.dump_outputs(str(tmp_path / "a"), {"images": t})
+    bench.dump_outputs(str(tmp_path / "b"), {"images": t})
+    assert sorted(os.listdir(tmp_path / "a")) == ["images_sample.npy"]
+    s, s2 = np.load(tmp_path / "a" / "images_sample.npy"), np.load(tmp_path / "b" / "images_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (1024,) and np.array_equal(s, s2)
+    assert (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < 10000 and (s == np.round(s)).all(), "distinct elements, in index order"
+    small = torch.randn(3, 5, dtype=torch.float16)
+    bench.dump_outputs(str(tmp_path / "c"), {"images": small})
+    assert np.array_equal(np.load(tmp_path / "c" / "images.npy"), small.float().numpy())
 
 
 def test_plan_file_export_cli(emu_lib, tmp_path):
