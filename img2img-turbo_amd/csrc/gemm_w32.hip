@@ -20,6 +20,7 @@
 //     are half-exchanged with v_permlane32_swap so that every lane stores (and fetches the residual as) 16 bytes.
 // 16-bit dtypes only; the exact-f32 parity mode, split-K shapes and everything with a gather stay on gemm_dma.hip.
 #include <stdlib.h>
+#include <type_traits>
 
 #include "i2i_dev.h"
 #include "launch.h"
@@ -272,6 +273,25 @@ __global__ __launch_bounds__(G32_NW * 64, 1) void gemm_w32_kernel(const i2i_igem
     for (int i = 0; i < (LNF ? FMW : 1); ++i) { ls[i] = 0.f; lq[i] = 0.f; }
     tx2 ones2;
     ones2[0] = (T)1.0f; ones2[1] = (T)1.0f;
+    // LNSHIFT (fp16): the sums are taken of x - pivot (one v_pk_add_f16 per element pair, exact by Sterbenz when the row sits on a DC
+    // offset): var = E[(x-p)^2] - E[x-p]^2 no longer cancels mu^2 against mu^2 in fp32.  The pivot is the MEDIAN of the row's first, middle
+    // and last element: one of them alone may be an outlier channel (or 0 on an offset row), and a pivot r sigma from the mean leaves the
+    // sums as exposed as unshifted ones at an offset of r sigma (r <= sqrt(K) for any element of the row).  The plain sums
+    // lose mu^2 / var * 2^-24 * sqrt(K/4) of the variance -- at mu = 100 sigma that is ~0.5 % of rstd, under bf16's own rounding step but
+    // 2 - 6 x the error of the unfused LayerNorm + linear pair in fp16 (tests/opcheck.py check_ln_gemm).
+    constexpr bool LNSHIFT = LNF && std::is_same<T, _Float16>::value;
+    tx2 piv2[LNSHIFT ? FMW : 1];
+    if constexpr (LNSHIFT) {
+#pragma unroll
+        for (int i = 0; i < FMW; ++i) {
+            int m = m0 + wave * WTM + i * 32 + l31;
+            m = m < p.M ? m : p.M - 1;                    // (the clamp of the row DMAs above)
+            const T* row = (const T*)p.a0 + (int64_t)m * p.lda0;
+            const float e0 = (float)row[0], e1 = (float)row[p.K / 2], e2 = (float)row[p.K - 1];
+            const T pv = (T)fmaxf(fminf(e0, e1), fminf(fmaxf(e0, e1), e2));      // median of three (exact: it IS one of them)
+            piv2[i][0] = pv; piv2[i][1] = pv;
+        }
+    }
 
     // The batch of stage s + RING (OPB pieces per wave) is issued in the window that opens after barrier P_s: PPS + PREM
     // pieces in the last k16 step of stage s (window slot 0), PPS in each of the k16 steps 0 .. KQ-2 of stage s + 1.
@@ -305,11 +325,12 @@ __global__ __launch_bounds__(G32_NW * 64, 1) void gemm_w32_kernel(const i2i_igem
                 for (int h = 0; h < 4; ++h) {
                     tx2 d;
                     d[0] = xf[cur][i][2 * h]; d[1] = xf[cur][i][2 * h + 1];
+                    if constexpr (LNSHIFT) d = d - piv2[i];
                     ls[i] = g32_dot2(d, ones2, ls[i]);
                     lq[i] = g32_dot2(d, d, lq[i]);
                 }
         }
-        constexpr int TOT = NRD + pn, NVAL = LNF ? 8 * FMW : 0;
+        constexpr int TOT = NRD + pn, NVAL = LNF ? (LNSHIFT ? 12 : 8) * FMW : 0;
         static_for_g<NMM>([&](auto mc) __attribute__((always_inline)) {
             constexpr int m = decltype(mc)::value;
             constexpr int lo = (TOT * m) / NMM, hi = (TOT * (m + 1)) / NMM;
@@ -387,8 +408,10 @@ __global__ __launch_bounds__(G32_NW * 64, 1) void gemm_w32_kernel(const i2i_igem
             float s0 = ls[i], s1 = ls[i], q0 = lq[i], q1 = lq[i];
             half_swap(s0, s1);                             // lanes 0-31: (own, partner's); lanes 32-63: (partner's, own)
             half_swap(q0, q1);
-            const float mu = (s0 + s1) * invk;
-            const float var = fmaxf((q0 + q1) * invk - mu * mu, 0.f);
+            const float ms = (s0 + s1) * invk;              // mean of x (LNSHIFT: of x - pivot)
+            const float var = fmaxf((q0 + q1) * invk - ms * ms, 0.f);
+            float mu = ms;
+            if constexpr (LNSHIFT) mu += (float)piv2[i][0];
             ra[i] = rsqrtf(var + p.ln_eps);
             rb[i] = -ra[i] * mu;
         }

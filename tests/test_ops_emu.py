@@ -624,3 +624,118 @@ def test_narrow_input_conv(emu_lib, dtype):
     oc.check_conv(emu_lib, "cpu", dtype, n=1, cin=8, cout=128, h=8, w=32, tile=60, seed=4)                    # all 8 input channels live
     oc.check_conv_gn_part(emu_lib, "cpu", dtype, n=2, cin=3, cout=128, h=16, w=64, groups=32, tile=60, res=False)
     oc.check_conv_gn_part(emu_lib, "cpu", dtype, n=1, cin=3, cout=128, h=12, w=40, groups=16, tile=60, res=False, seed=2)
+
+
+# ---------------------------------------------------------------- adversarial numerics: fp64 references, derived per-element bounds
+# (opcheck.attention_bound / check_attention_scores / check_softmax / check_layernorm / check_ln_gemm: the data-dependent branches of
+# the fused softmax and LayerNorm kernels)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_product_calling_conventions(emu_lib, dtype):
+    """What the planner and the text tower pass: q carrying scale * log2(e) with scale = ln 2, q and k read out of one [q|k] buffer
+    (ldq = ldk = 2C), and the CLIP tower's causal shape (batch 2, 16 heads, 77 tokens; f32: the register kernel, 16-bit: the LDS-DMA
+    kernel, which re-rounds q because the tower passes scale = 1/8)."""
+    oc.check_attention(emu_lib, "cpu", dtype, batch=2, heads=16, tq=77, tk=77, fused_qk=True, causal=True)
+    oc.check_attention(emu_lib, "cpu", dtype, batch=1, heads=2, tq=77, tk=77, fused_qk=True, causal=True, prescaled=True, seed=1)
+    oc.check_attention(emu_lib, "cpu", dtype, batch=2, heads=2, tq=130, tk=130, fused_qk=True, prescaled=True)
+    oc.check_attention(emu_lib, "cpu", dtype, prescaled=True, seed=2)
+    oc.check_attention(emu_lib, "cpu", dtype, batch=1, heads=2, tq=130, tk=130, fused_qk=True, seed=3)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("qf", ["1", "2"])
+def test_attention_causal_beyond_one_tile(emu_lib, dtype, qf, monkeypatch):
+    """causal = 1 past 128 tokens: waves see key tiles that are masked for all their queries (tile maximum -1e30) together with the
+    ragged last tile; 64- and 128-query workgroups."""
+    monkeypatch.setenv("I2I_ATT_QF", qf)
+    oc.check_attention(emu_lib, "cpu", dtype, batch=1, heads=2, tq=200, tk=200, causal=True)
+    oc.check_attention(emu_lib, "cpu", dtype, batch=1, heads=1, tq=325, tk=325, causal=True, fused_qk=True, seed=1)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_attention_causal_with_key_splits_is_refused(emu_lib, dtype):
+    oc.check_attention_causal_ksplit_refused(emu_lib, "cpu", dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("qf", ["1", "2"])
+@pytest.mark.parametrize("ksplit", [0, 2, 4])
+@pytest.mark.parametrize("pattern", oc.ATT_PATTERNS)
+def test_attention_score_patterns(emu_lib, dtype, qf, ksplit, pattern, monkeypatch):
+    """attention_dma_kernel's lazy reference and the merge of key splits on designed score patterns (check_attention_scores)."""
+    monkeypatch.setenv("I2I_ATT_QF", qf)
+    oc.check_attention_scores(emu_lib, "cpu", dtype, pattern, ksplit=ksplit)
+    if pattern == "split_place" and ksplit == 4:
+        oc.check_attention_scores(emu_lib, "cpu", dtype, pattern, ksplit=4, tk=100)        # two key tiles over four splits: two empty
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("ksplit", [0, 2, 4])
+@pytest.mark.parametrize("pattern", oc.ATT_PATTERNS)
+def test_attention_score_patterns_wide_head(emu_lib, dtype, ksplit, pattern):
+    """The same patterns through attention_wide_kernel (d = 512: running maximum per 32-key tile) and attention_combine_kernel."""
+    oc.check_attention_scores(emu_lib, "cpu", dtype, pattern, d=512, ksplit=ksplit, tq=64 if pattern != "spike_query" else 128)
+    if pattern == "split_place" and ksplit == 4:
+        oc.check_attention_scores(emu_lib, "cpu", dtype, pattern, d=512, ksplit=4, tk=40, tq=32)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("flavour", ["span", "const", "dominant"])
+def test_softmax_adversarial_rows(emu_lib, dtype, flavour):
+    oc.check_softmax(emu_lib, "cpu", dtype, rows=13, cols=77, ldp=80, flavour=flavour)                  # three-pass kernel
+    oc.check_softmax(emu_lib, "cpu", dtype, rows=9, cols=256, ldp=256, flavour=flavour, seed=1)          # register-resident kernel
+    oc.check_softmax(emu_lib, "cpu", dtype, rows=6, cols=1024, ldp=1032, flavour=flavour, scale=1.0, seed=2)
+
+
+LN_OFFSETS = [8.0, 32.0, 100.0]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_layernorm_on_a_dc_offset(emu_lib, dtype):
+    """Standalone LayerNorm, rows on a DC offset of 0 / +-8 / +-32 / +-100 sigma in one launch, the three widths (1, 2, 4 chunks per lane)."""
+    for c in (320, 640, 1280):
+        oc.check_layernorm(emu_lib, "cpu", dtype, rows=21, c=c, mu_sigma=torch.tensor([0.0, 8.0, -8.0, 32.0, -32.0, 100.0, -100.0]), seed=c)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 640, 1280])
+@pytest.mark.parametrize("form", ["plain", "trans", "geglu"])
+def test_layernorm_fold_on_a_dc_offset(emu_lib, dtype, cin, form):
+    """The LayerNorm fold of the wide GEMM at mu^2 / var up to 1e4 (|mu/sigma| = 0, 8, 32, 100; both signs and 0 in every launch)
+    against the floor of the unfused pair; 300 and 1000 are measured and printed, not gated."""
+    kw = dict(plain=dict(nq=160, rows=200, tile=52), trans=dict(nq=320, nv=160, rows=264, tile=52), geglu=dict(nq=320, geglu=True, rows=200, tile=55))[form]
+    for v in LN_OFFSETS:
+        oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, mu_sigma=torch.tensor([0.0, v, -v]), seed=int(v), **kw)
+    for v in (300.0, 1000.0):
+        oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, mu_sigma=torch.tensor([v, -v]), seed=int(v), gate=False, **kw)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 1280])
+@pytest.mark.parametrize("col0", ["zero", "outlier"])
+def test_layernorm_fold_with_an_unrepresentative_first_element(emu_lib, dtype, cin, col0):
+    """The fp16 fold shifts its sums by the median of the row's first, middle and last element: the first one overwritten by 0 and by
+    a 30 sigma outlier, on rows at 0 and +-100 sigma, stays inside the floor gates (check_ln_gemm, col0)."""
+    oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, nq=160, rows=200, tile=52, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=5)
+    oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, nq=320, nv=160, rows=264, tile=52, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=6)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 1280])
+@pytest.mark.parametrize("col0", ["zero2", "outlier2"])
+def test_layernorm_fold_with_an_unrepresentative_pivot(emu_lib, dtype, cin, col0):
+    """Two of the three elements the fp16 pivot is the median of (columns 0 and K/2) overwritten: the pivot is then up to sqrt(K) sigma
+    from the mean.  fp16: finite, measured and printed beside the floor (include/i2i_turbo.h at ln_cs and DESIGN.md section 4 quote the
+    figures); bf16 takes plain sums whatever the pivot and keeps the floor gates (check_ln_gemm, col0)."""
+    gate = dtype != torch.float16
+    oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, nq=160, rows=200, tile=52, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=7, gate=gate)
+    oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, nq=320, nv=160, rows=264, tile=52, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=8, gate=gate)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 1280])
+def test_layernorm_fold_on_constant_rows(emu_lib, dtype, cin):
+    """Rows of variance exactly 0 on offsets of both signs: the one-pass variance is fp32 rounding noise of either sign and must be
+    clamped, not fed to rsqrt; the output is the folded bias within the derived bound (check_ln_gemm, flat)."""
+    consts = torch.tensor([100.0, -100.0, 37.0, -3.0, 0.5, 0.0, 250.0, -77.0, 19.0, 141.0, -63.0])
+    oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, nq=160, rows=200, tile=52, mu_sigma=consts, flat=True)
+    oc.check_ln_gemm(emu_lib, "cpu", dtype, cin=cin, nq=320, nv=160, rows=264, tile=52, mu_sigma=consts, flat=True, seed=1)

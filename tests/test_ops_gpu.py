@@ -378,3 +378,105 @@ def test_gn_apply_one_and_two_sources(gpu_lib, dtype):
     oc.check_gn_apply(gpu_lib, "cuda", dtype, n=2, c=320, h=64, w=64)
     oc.check_gn_apply(gpu_lib, "cuda", dtype, n=2, c=1280, c1=640, h=32, w=32, seed=1)     # up-block resnet input
     oc.check_gn_apply(gpu_lib, "cuda", dtype, n=1, c=320, c1=320, h=63, w=65, act=0, seed=2)
+
+
+# ---------------------------------------------------------------- adversarial numerics: fp64 references, derived per-element bounds
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_product_calling_conventions(gpu_lib, dtype):
+    """The planner's and the text tower's calling conventions at the forward's shapes: pre-scaled q with scale = ln 2 out of a fused
+    [q|k] buffer (UNet self-attention, 1024 and 4096 tokens), the CLIP tower (batch 2, 16 heads, 77 tokens, fused, causal, scale 1/8)."""
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=2, heads=16, tq=77, tk=77, fused_qk=True, causal=True)
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=2, heads=16, tq=77, tk=77, fused_qk=True, causal=True, prescaled=True, seed=1)
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=2, heads=10, tq=1024, tk=1024, fused_qk=True, prescaled=True)
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=1, heads=5, tq=4096, tk=4096, fused_qk=True, prescaled=True, seed=2)
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=2, heads=10, tq=256, tk=77, prescaled=True, seed=3)          # cross-attention
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_causal_beyond_one_tile(gpu_lib, dtype):
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=1, heads=2, tq=200, tk=200, causal=True)
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=2, heads=3, tq=325, tk=325, causal=True, fused_qk=True, seed=1)
+    oc.check_attention(gpu_lib, "cuda", dtype, batch=8, heads=16, tq=325, tk=325, causal=True, seed=2)             # 128-query workgroups
+    if dtype != torch.float32:
+        oc.check_attention_causal_ksplit_refused(gpu_lib, "cuda", dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("pattern", oc.ATT_PATTERNS)
+def test_attention_score_patterns(gpu_lib, dtype, pattern, monkeypatch):
+    """Designed score patterns (check_attention_scores) on the real kernels: d = 64 at a small grid and at one that fills the chip
+    (both sides of the launcher's 128-query rule; the spiked query then sits in the last query tile), d = 512, without and with key
+    splits.  The wave width is FORCED (I2I_ATT_QF, as on the emulator) so that the trigger map replays what really ran: 64-query
+    workgroups at the small grid, 128-query ones at both."""
+    qbase = (2048 if pattern == "spike_query" else 6144) - 128
+    for ksplit in (0, 2, 4):
+        monkeypatch.setenv("I2I_ATT_QF", "1")
+        assert oc.check_attention_scores(gpu_lib, "cuda", dtype, pattern, ksplit=ksplit) == 1
+        monkeypatch.setenv("I2I_ATT_QF", "2")
+        assert oc.check_attention_scores(gpu_lib, "cuda", dtype, pattern, ksplit=ksplit) == 2
+        assert oc.check_attention_scores(gpu_lib, "cuda", dtype, pattern, ksplit=ksplit, qbase=qbase) == 2
+        oc.check_attention_scores(gpu_lib, "cuda", dtype, pattern, d=512, ksplit=ksplit, tq=256)
+    monkeypatch.setenv("I2I_ATT_QF", "1")
+    if pattern == "split_place":        # more splits than key tiles
+        oc.check_attention_scores(gpu_lib, "cuda", dtype, pattern, ksplit=4, tk=100)
+        oc.check_attention_scores(gpu_lib, "cuda", dtype, pattern, d=512, ksplit=4, tk=40)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("flavour", ["span", "const", "dominant"])
+def test_softmax_adversarial_rows(gpu_lib, dtype, flavour):
+    oc.check_softmax(gpu_lib, "cuda", dtype, rows=500, cols=77, ldp=80, flavour=flavour)
+    oc.check_softmax(gpu_lib, "cuda", dtype, rows=130, cols=1024, ldp=1032, flavour=flavour, seed=1)
+    oc.check_softmax(gpu_lib, "cuda", dtype, rows=259, cols=4096, ldp=4096, flavour=flavour, scale=1.0, seed=2)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_layernorm_on_a_dc_offset(gpu_lib, dtype):
+    for c, rows in ((320, 4099), (640, 1031), (1280, 1000), (1024, 77)):
+        oc.check_layernorm(gpu_lib, "cuda", dtype, rows=rows, c=c, mu_sigma=torch.tensor([0.0, 8.0, -8.0, 32.0, -32.0, 100.0, -100.0]), seed=c)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 640, 1280])
+def test_layernorm_fold_on_a_dc_offset(gpu_lib, dtype, cin):
+    """The LayerNorm fold at the forward's three widths and three forms, |mu/sigma| = 0 / 8 / 32 / 100 gated against the floor of the
+    unfused pair, 300 / 1000 measured (DESIGN.md section 4 tabulates the printed lines)."""
+    rows = {320: 4096, 640: 1024, 1280: 264}[cin]
+    forms = (dict(nq=cin), dict(nq=2 * cin, nv=cin), dict(nq=8 * cin, geglu=True))
+    for kw in forms:
+        for v in (8.0, 32.0, 100.0):
+            oc.check_ln_gemm(gpu_lib, "cuda", dtype, rows=rows, cin=cin, tile=50, mu_sigma=torch.tensor([0.0, v, -v]), seed=int(v), **kw)
+        for v in (300.0, 1000.0):
+            oc.check_ln_gemm(gpu_lib, "cuda", dtype, rows=rows, cin=cin, tile=50, mu_sigma=torch.tensor([v, -v]), seed=int(v), gate=False, **kw)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 1280])
+@pytest.mark.parametrize("col0", ["zero", "outlier"])
+def test_layernorm_fold_with_an_unrepresentative_first_element(gpu_lib, dtype, cin, col0):
+    """The fp16 fold shifts its sums by the median of the row's first, middle and last element: the first one overwritten by 0 and by
+    a 30 sigma outlier, on rows at 0 and +-100 sigma, stays inside the floor gates (check_ln_gemm, col0)."""
+    oc.check_ln_gemm(gpu_lib, "cuda", dtype, cin=cin, nq=cin, rows=1024, tile=50, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=5)
+    oc.check_ln_gemm(gpu_lib, "cuda", dtype, cin=cin, nq=2 * cin, nv=cin, rows=1024, tile=50, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=6)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 1280])
+@pytest.mark.parametrize("col0", ["zero2", "outlier2"])
+def test_layernorm_fold_with_an_unrepresentative_pivot(gpu_lib, dtype, cin, col0):
+    """Two of the three elements the fp16 pivot is the median of (columns 0 and K/2) overwritten: the pivot is then up to sqrt(K) sigma
+    from the mean.  fp16: finite, measured and printed beside the floor (include/i2i_turbo.h at ln_cs and DESIGN.md section 4 quote the
+    figures); bf16 takes plain sums whatever the pivot and keeps the floor gates (check_ln_gemm, col0)."""
+    gate = dtype != torch.float16
+    oc.check_ln_gemm(gpu_lib, "cuda", dtype, cin=cin, nq=cin, rows=1024, tile=50, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=7, gate=gate)
+    oc.check_ln_gemm(gpu_lib, "cuda", dtype, cin=cin, nq=2 * cin, nv=cin, rows=1024, tile=50, mu_sigma=torch.tensor([0.0, 100.0, -100.0]), col0=col0, seed=8, gate=gate)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("cin", [320, 1280])
+def test_layernorm_fold_on_constant_rows(gpu_lib, dtype, cin):
+    """Rows of variance exactly 0 on offsets of both signs: the one-pass variance is fp32 rounding noise of either sign and must be
+    clamped, not fed to rsqrt; the output is the folded bias within the derived bound (check_ln_gemm, flat)."""
+    consts = torch.tensor([100.0, -100.0, 37.0, -3.0, 0.5, 0.0, 250.0, -77.0, 19.0, 141.0, -63.0])
+    oc.check_ln_gemm(gpu_lib, "cuda", dtype, cin=cin, nq=160, rows=1024, tile=50, mu_sigma=consts, flat=True)
+    oc.check_ln_gemm(gpu_lib, "cuda", dtype, cin=cin, nq=320, nv=160, rows=1024, tile=50, mu_sigma=consts, flat=True, seed=1)
