@@ -17,9 +17,10 @@ OP_NCHW_TO_NHWC, OP_NHWC_TO_NCHW, OP_POSTERIOR, OP_DDPM_POSTQUANT, OP_ATTENTION,
 OP_LORA_MERGE = 12
 OP_RESIZE_U8 = 13
 OP_NOP = 14
+OP_CANNY_U8 = 15
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
-ABI_VERSION = 10         # include/i2i_turbo.h I2I_ABI_VERSION this binding was written for
+ABI_VERSION = 11         # include/i2i_turbo.h I2I_ABI_VERSION this binding was written for
 
 
 class IgemmParams(C.Structure):
@@ -101,6 +102,11 @@ class ResizeU8Params(C.Structure):
                 ("bounds", vp), ("coeffs", vp)]
 
 
+class CannyU8Params(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("n", i32), ("h", i32), ("w", i32), ("c", i32), ("out_c", i32), ("low", i32), ("high", i32),
+                ("thr_dev", vp), ("ws", vp)]
+
+
 class NopParams(C.Structure):
     _fields_ = [("unused", i32)]
 
@@ -110,7 +116,7 @@ class _OpUnion(C.Union):
                 ("layernorm", LayerNormParams), ("softmax", SoftmaxParams), ("attention", AttentionParams),
                 ("to_nhwc", NchwToNhwcParams), ("to_nchw", NhwcToNchwParams), ("embed", EmbedParams),
                 ("posterior", PosteriorParams), ("ddpm", DdpmParams), ("lora_merge", LoraMergeParams), ("resize_u8", ResizeU8Params),
-                ("nop", NopParams)]
+                ("nop", NopParams), ("canny_u8", CannyU8Params)]
 
 
 class Op(C.Structure):
@@ -120,11 +126,11 @@ class Op(C.Structure):
 _FIELD_OF = {OP_IGEMM: "igemm", OP_GN_STATS: "gn_stats", OP_GN_APPLY: "gn_apply", OP_LAYERNORM: "layernorm",
              OP_SOFTMAX: "softmax", OP_ATTENTION: "attention", OP_NCHW_TO_NHWC: "to_nhwc",
              OP_NHWC_TO_NCHW: "to_nchw", OP_POSTERIOR: "posterior", OP_DDPM_POSTQUANT: "ddpm", OP_EMBED: "embed",
-             OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop"}
+             OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8"}
 
 EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", "i2i_igemm", "i2i_igemm_gn_parts", "i2i_igemm_route", "i2i_gn_stats",
            "i2i_gn_apply", "i2i_nop", "i2i_calib_mfma", "i2i_calib_stream", "i2i_layernorm", "i2i_softmax", "i2i_attention", "i2i_nchw_to_nhwc",
-           "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_run", "i2i_run_timed",
+           "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_canny_ws_bytes", "i2i_run", "i2i_run_timed",
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy"]
 
@@ -178,9 +184,11 @@ class Library:
         L.i2i_last_error.restype = C.c_char_p
         L.i2i_sizeof_op.restype = C.c_size_t
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
-                     "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8"):
+                     "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
+        L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.i2i_canny_ws_bytes.restype = C.c_size_t
         L.i2i_nop.argtypes = [vp]
         L.i2i_calib_mfma.argtypes = [C.c_int, C.c_int, vp, vp, vp]
         L.i2i_calib_stream.argtypes = [vp, vp, C.c_size_t, vp]
@@ -209,6 +217,10 @@ class Library:
     def check(self, rc):
         if rc != 0:
             raise I2IError("i2i error %d: %s" % (rc, self.lib.i2i_last_error().decode()))
+
+    def canny_ws_bytes(self, n, h, w):
+        """Bytes of the workspace i2i_canny_u8 needs for an [n, h, w, c] batch."""
+        return int(self.lib.i2i_canny_ws_bytes(int(n), int(h), int(w)))
 
     # ---- programs -------------------------------------------------------------------------------
     def igemm_gn_parts(self, params, dtype_code, groups):

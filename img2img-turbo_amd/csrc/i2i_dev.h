@@ -125,6 +125,21 @@ __device__ __forceinline__ int up_src(int i, int in, int up, int ups) {
     return j < in - 1 ? j : in - 1;
 }
 
+// ---- words that workgroups of ONE launch share (the union-find parent array of the Canny merge, resize.hip): agent-scope atomics only --
+// a plain store behind a fence is not reliably seen from another XCD.  The emulator runs a launch's threads as fibers of one host
+// thread, so plain accesses are atomic there.
+#ifdef I2I_EMU
+__device__ __forceinline__ int32_t agent_load_i32(const int32_t* p) { return *(const volatile int32_t*)p; }
+__device__ __forceinline__ int32_t agent_min_i32(int32_t* p, int32_t v) {     // returns the old value
+    const int32_t old = *p;
+    if (v < old) *p = v;
+    return old;
+}
+#else
+__device__ __forceinline__ int32_t agent_load_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int32_t agent_min_i32(int32_t* p, int32_t v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#endif
+
 // ---- explicit synchronisation for LDS-DMA pipelines (cdna_hip_programming.md section 5: raw s_barrier +
 // counted waits; __syncthreads() would drain the DMA queue with vmcnt(0) at every barrier).
 // The CPU emulator (tests/emu, I2I_EMU) executes copies synchronously, so the waits are no-ops there.

@@ -79,6 +79,7 @@ const std::vector<size_t>& ptr_fields(int opcode) {
     static const std::vector<size_t> lora = {PF(lora_merge, dst), PF(lora_merge, w0), PF(lora_merge, a), PF(lora_merge, b), PF(lora_merge, rg),
                                              PF(lora_merge, kscale), PF(lora_merge, kshift), PF(lora_merge, bias0), PF(lora_merge, colsum), PF(lora_merge, bias_out)};
     static const std::vector<size_t> resize = {PF(resize_u8, src), PF(resize_u8, dst), PF(resize_u8, bounds), PF(resize_u8, coeffs)};
+    static const std::vector<size_t> canny = {PF(canny_u8, src), PF(canny_u8, dst), PF(canny_u8, thr_dev), PF(canny_u8, ws)};
     switch (opcode) {
         case I2I_OP_IGEMM: return igemm;
         case I2I_OP_GN_STATS: return gn_stats;
@@ -93,6 +94,7 @@ const std::vector<size_t>& ptr_fields(int opcode) {
         case I2I_OP_EMBED: return embed;
         case I2I_OP_LORA_MERGE: return lora;
         case I2I_OP_RESIZE_U8: return resize;
+        case I2I_OP_CANNY_U8: return canny;
         default: return none;
     }
 }

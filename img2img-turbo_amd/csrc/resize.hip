@@ -1,10 +1,15 @@
-// Device-side LANCZOS resize of uint8 HWC image batches, bit-identical to Pillow's Image.resize(..., Image.LANCZOS)
+// Device-side uint8 image pre-processing of the callers: LANCZOS resize, Canny.
+//
+// LANCZOS resize of uint8 HWC image batches, bit-identical to Pillow's Image.resize(..., Image.LANCZOS)
 // (the reference resizes on the host: src/inference_paired.py:38-41 to a multiple of 8, src/inference_unpaired.py:40,53 to the
 // model size and back).  HBM-bound byte work: Pillow's two separable passes (horizontal, then vertical) in 32-bit integer
 // arithmetic on 22-bit fixed-point weights; the per-coordinate tap windows and weights come from the host
 // (img2img_turbo_amd/image_ops.py restates Pillow's precompute_coeffs / normalize_coeffs_8bpc in double precision).
 //   out = clip8((2^21 + sum_t in[first + t] * k[t]) >> 22)
 // Horizontal pass: a thread per output pixel, one 8-byte load per tap; vertical pass: a thread per 4 bytes of the flattened row.
+//
+// Canny (second half of the file): cv::Canny for 8-bit input, aperture 3, L1 gradient, in integer arithmetic (the contract is the
+// comment of i2i_canny_u8_params in include/i2i_turbo.h; the reference runs it on the host: src/image_prep.py:6-12).
 #include "i2i_dev.h"
 #include "launch.h"
 
@@ -111,4 +116,319 @@ extern "C" int i2i_resize_u8(const i2i_resize_u8_params* p, int dtype, void* str
         else hipLaunchKernelGGL(resize_v_u8_kernel<1>, dim3(blocks((int64_t)p->n * p->nout * rowb)), dim3(256), 0, s, *p);
     }
     return i2i::check_launch("resize_u8");
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Canny.  Five launches, whatever the image holds:
+//   1 canny_nms_kernel    a workgroup per 64 x 16 tile: input with a 2-pixel halo in LDS (a pixel = one dword), Sobel + channel choice
+//                         on the tile with a 1-pixel halo, non-maximum suppression -> class map (0 none, 1 weak, 2 strong)
+//   2 canny_label_kernel  connected components of candidates INSIDE a tile: min-label propagation with pointer jumping in LDS to the
+//                         tile-local fixpoint; label[p] = global pixel index of the tile-local root (-1: no candidate), flag[p] = 0
+//   3 canny_merge_kernel  candidates on both sides of a tile edge: lock-free union of their roots (atomic min on the larger root, retry
+//                         on change).  `label` is a union-find parent array whose entries only ever decrease (parent[p] <= p).
+//   4 canny_flag_kernel   every strong pixel marks the root of its component
+//   5 canny_emit_kernel   edge = candidate whose root is marked
+// Hysteresis is therefore exact for chains of any length across any number of tiles, with no grid-wide wait and no pass count that
+// depends on the image: the loop of (2) is bounded by the tile's pixel count, every union-find walk by the image's (labels strictly
+// decrease along a walk).  Inside launch 3 the parent words are touched only by agent-scope atomics (i2i_dev.h agent_*); everything
+// written with plain stores (class map, initial labels, flags) is read by a LATER launch only.  Workspace: label int32[P] | flag
+// int32[P] | class uint8[P], P = n*h*w; every word is written before it is read in each run (nothing to zero, no state kept).
+namespace {
+
+constexpr int CTW = 64, CTH = 16, CTPIX = CTW * CTH;         // tile; 256 threads own 4 pixels each
+constexpr int CPW = CTW + 4, CPH = CTH + 4;                  // input region (2-pixel halo)
+constexpr int CMW = CTW + 2, CMH = CTH + 2;                  // gradient / label region (1-pixel halo)
+constexpr int CANNY_INF = 1 << 20;                           // label of a non-candidate in the tile-local propagation
+
+struct canny_ws {
+    int32_t* label; int32_t* flag; uint8_t* cls;
+};
+__host__ __device__ __forceinline__ canny_ws canny_carve(void* ws, int64_t P) {
+    canny_ws r;
+    r.label = (int32_t*)ws;
+    r.flag = r.label + P;
+    r.cls = (uint8_t*)(r.flag + P);
+    return r;
+}
+
+struct canny_tile { int img, x0, y0; };
+__device__ __forceinline__ canny_tile canny_tile_of(const i2i_canny_u8_params& p, int t) {
+    const int ntx = (p.w + CTW - 1) / CTW, nty = (p.h + CTH - 1) / CTH;
+    canny_tile r;
+    r.x0 = (t % ntx) * CTW;
+    r.y0 = ((t / ntx) % nty) * CTH;
+    r.img = t / (ntx * nty);
+    return r;
+}
+
+__global__ __launch_bounds__(256) void canny_nms_kernel(const i2i_canny_u8_params p) {
+    const int64_t P = (int64_t)p.n * p.h * p.w;
+    const canny_ws ws = canny_carve(p.ws, P);
+    const canny_tile t = canny_tile_of(p, (int)blockIdx.x);
+    const int tid = (int)threadIdx.x;
+    int low = p.thr_dev ? p.thr_dev[0] : p.low, high = p.thr_dev ? p.thr_dev[1] : p.high;
+    if (low > high) { const int s = low; low = high; high = s; }
+
+    uint32_t* pix = (uint32_t*)i2i_smem;                     // [CPH][CPW], channel ch in byte ch
+    int16_t* mg = (int16_t*)(pix + CPH * CPW);               // [CMH][CMW] each
+    int16_t* gx = mg + CMH * CMW;
+    int16_t* gy = gx + CMH * CMW;
+
+    // input with BORDER_REPLICATE (clamped coordinates).  A pixel's c <= 4 bytes come as ONE 8-byte load from the enclosing aligned
+    // dword pair (the tensor base is 4-byte aligned), as in resize_h_u8_kernel; the last pixels of the batch byte by byte
+    const uint8_t* __restrict__ base = (const uint8_t*)p.src;
+    const int64_t nbytes = P * p.c;
+    for (int i = tid; i < CPH * CPW; i += 256) {
+        const int ly = i / CPW, lx = i % CPW;
+        int yy = t.y0 + ly - 2, xx = t.x0 + lx - 2;
+        yy = yy < 0 ? 0 : (yy > p.h - 1 ? p.h - 1 : yy);
+        xx = xx < 0 ? 0 : (xx > p.w - 1 ? p.w - 1 : xx);
+        const int64_t a = (((int64_t)t.img * p.h + yy) * p.w + xx) * p.c;
+        uint32_t v = 0;
+        if ((a & ~(int64_t)3) + 8 <= nbytes) {
+            const uint32_t* q = (const uint32_t*)(base + (a & ~(int64_t)3));
+            v = (uint32_t)((((uint64_t)q[0]) | ((uint64_t)q[1] << 32)) >> (8 * (int)(a & 3)));
+        } else {
+            for (int ch = 0; ch < p.c; ++ch) v |= (uint32_t)base[a + ch] << (8 * ch);
+        }
+        pix[i] = v;
+    }
+    __syncthreads();
+
+    // Sobel per channel, the channel of the largest |dx| + |dy| (the lowest one on a tie); magnitude 0 outside the image
+    for (int i = tid; i < CMH * CMW; i += 256) {
+        const int ly = i / CMW, lx = i % CMW;
+        const int yy = t.y0 + ly - 1, xx = t.x0 + lx - 1;
+        int bm = 0, bdx = 0, bdy = 0;
+        if (yy >= 0 && yy < p.h && xx >= 0 && xx < p.w) {
+            const uint32_t* r0 = pix + ly * CPW + lx;        // row above, column to the left
+            const uint32_t* r1 = r0 + CPW;
+            const uint32_t* r2 = r1 + CPW;
+            const uint32_t p00 = r0[0], p01 = r0[1], p02 = r0[2], p10 = r1[0], p12 = r1[2], p20 = r2[0], p21 = r2[1], p22 = r2[2];
+            bm = -1;
+#pragma unroll
+            for (int ch = 0; ch < 4; ++ch) {
+                if (ch < p.c) {
+                    const int s = 8 * ch;
+                    const int a00 = (p00 >> s) & 0xff, a01 = (p01 >> s) & 0xff, a02 = (p02 >> s) & 0xff, a10 = (p10 >> s) & 0xff;
+                    const int a12 = (p12 >> s) & 0xff, a20 = (p20 >> s) & 0xff, a21 = (p21 >> s) & 0xff, a22 = (p22 >> s) & 0xff;
+                    const int dx = (a02 + 2 * a12 + a22) - (a00 + 2 * a10 + a20);
+                    const int dy = (a20 + 2 * a21 + a22) - (a00 + 2 * a01 + a02);
+                    const int m = (dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy);
+                    if (m > bm) { bm = m; bdx = dx; bdy = dy; }
+                }
+            }
+        }
+        mg[i] = (int16_t)bm;
+        gx[i] = (int16_t)bdx;
+        gy[i] = (int16_t)bdy;
+    }
+    __syncthreads();
+
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = tid + k * 256, ly = i / CTW, lx = i % CTW;
+        const int yy = t.y0 + ly, xx = t.x0 + lx;
+        if (yy >= p.h || xx >= p.w) continue;
+        const int16_t* c = mg + (ly + 1) * CMW + lx + 1;
+        const int m = c[0];
+        int cls = 0;
+        if (m > low) {
+            const int dx = gx[(ly + 1) * CMW + lx + 1], dy = gy[(ly + 1) * CMW + lx + 1];
+            const int ax = dx < 0 ? -dx : dx, ay = (dy < 0 ? -dy : dy) << 15;
+            const int tg22x = ax * 13573, tg67x = tg22x + (ax << 16);
+            bool keep;
+            if (ay < tg22x) keep = m > c[-1] && m >= c[1];
+            else if (ay > tg67x) keep = m > c[-CMW] && m >= c[CMW];
+            else {
+                const int s = ((dx ^ dy) < 0) ? -1 : 1;
+                keep = m > c[-CMW - s] && m > c[CMW + s];
+            }
+            if (keep) cls = m > high ? 2 : 1;
+        }
+        ws.cls[((int64_t)t.img * p.h + yy) * p.w + xx] = (uint8_t)cls;
+    }
+}
+
+__global__ __launch_bounds__(256) void canny_label_kernel(const i2i_canny_u8_params p) {
+    const int64_t P = (int64_t)p.n * p.h * p.w;
+    const canny_ws ws = canny_carve(p.ws, P);
+    const canny_tile t = canny_tile_of(p, (int)blockIdx.x);
+    const int tid = (int)threadIdx.x;
+    int* lab = (int*)i2i_smem;                               // [CMH][CMW]: tile-local index of the smallest pixel known to be connected
+    int* chg = lab + CMH * CMW;                              // [2]: "some label moved" of the even / odd sweeps
+    for (int i = tid; i < CMH * CMW; i += 256) lab[i] = CANNY_INF;
+    if (tid == 0) chg[0] = chg[1] = 0;
+    __syncthreads();
+    int pos[4], cur[4];
+    int64_t g[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = tid + k * 256, ly = i / CTW, lx = i % CTW;
+        const int yy = t.y0 + ly, xx = t.x0 + lx;
+        pos[k] = (ly + 1) * CMW + lx + 1;
+        g[k] = (yy < p.h && xx < p.w) ? ((int64_t)t.img * p.h + yy) * p.w + xx : -1;
+        cur[k] = (g[k] >= 0 && ws.cls[g[k]] != 0) ? i : CANNY_INF;
+        lab[pos[k]] = cur[k];
+    }
+    __syncthreads();
+    // Sweep = every candidate takes the minimum over its 3 x 3 neighbourhood, then the label of THAT pixel (pointer jumping); reads and
+    // writes of a sweep are separated by barriers.  Labels never fall below their component's minimum and fall at least as fast as under
+    // plain propagation, which reaches the fixpoint within the longest geodesic of the tile (< CTPIX sweeps): the bound is never the exit.
+    for (int it = 0; it < CTPIX; ++it) {
+        int nl[4];
+        bool moved = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            nl[k] = cur[k];
+            if (cur[k] == CANNY_INF) continue;
+            const int* c = lab + pos[k];
+            int m = cur[k];
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) m = min(m, c[dy * CMW + dx]);
+            m = min(m, lab[(m / CTW + 1) * CMW + (m % CTW) + 1]);
+            nl[k] = m;
+            moved |= m < cur[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (nl[k] < cur[k]) lab[pos[k]] = cur[k] = nl[k];
+        if (moved) chg[it & 1] = 1;
+        if (tid == 0) chg[(it + 1) & 1] = 0;
+        __syncthreads();
+        if (!chg[it & 1]) break;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (g[k] < 0) continue;
+        int32_t root = -1;
+        if (cur[k] != CANNY_INF) root = (int32_t)((((int64_t)t.img * p.h + t.y0 + cur[k] / CTW) * p.w) + t.x0 + cur[k] % CTW);
+        ws.label[g[k]] = root;
+        ws.flag[g[k]] = 0;
+    }
+}
+
+// root of x in launch 3, where other workgroups lower parent words concurrently: atomic loads only; the walk strictly descends
+__device__ __forceinline__ int32_t canny_find_live(int32_t* parent, int32_t x) {
+    for (;;) {
+        const int32_t n = agent_load_i32(parent + x);
+        if (n == x) return x;
+        x = n;
+    }
+}
+// root of x once the parent array is final (launches 4 and 5)
+__device__ __forceinline__ int32_t canny_find(const int32_t* parent, int32_t x) {
+    for (;;) {
+        const int32_t n = parent[x];
+        if (n == x) return x;
+        x = n;
+    }
+}
+// Lock-free union: hang the larger root under the smaller one with an atomic min.  If the word was no longer a root (another union got
+// there first and left `old` < a in it) it now holds min(old, b) and the other of the two still has to be joined: go on with (old, b).
+// Every retry continues from a strictly smaller index.
+__device__ __forceinline__ void canny_union(int32_t* parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = canny_find_live(parent, a);
+        b = canny_find_live(parent, b);
+        if (a == b) return;
+        if (a < b) { const int32_t s = a; a = b; b = s; }
+        const int32_t old = agent_min_i32(parent + a, b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// a thread per pixel of the first row / first column of a tile (only those do anything): its candidate neighbours in the row above /
+// the column to the left lie in other tiles (diagonal tiles included)
+__global__ __launch_bounds__(256) void canny_merge_kernel(const i2i_canny_u8_params p) {
+    const int64_t P = (int64_t)p.n * p.h * p.w;
+    const canny_ws ws = canny_carve(p.ws, P);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P; i += (int64_t)gridDim.x * 256) {
+        const int x = (int)(i % p.w), y = (int)((i / p.w) % p.h);
+        const bool top = (y % CTH) == 0 && y > 0, left = (x % CTW) == 0 && x > 0;
+        if (!(top || left) || ws.cls[i] == 0) continue;
+        if (top) {
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (x + dx < 0 || x + dx >= p.w) continue;
+                const int64_t j = i - p.w + dx;
+                if (ws.cls[j] != 0) canny_union(ws.label, (int32_t)i, (int32_t)j);
+            }
+        }
+        if (left) {
+            for (int dy = -1; dy <= 1; ++dy) {
+                if (y + dy < 0 || y + dy >= p.h) continue;
+                const int64_t j = i + (int64_t)dy * p.w - 1;
+                if (ws.cls[j] != 0) canny_union(ws.label, (int32_t)i, (int32_t)j);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void canny_flag_kernel(const i2i_canny_u8_params p) {
+    const int64_t P = (int64_t)p.n * p.h * p.w;
+    const canny_ws ws = canny_carve(p.ws, P);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P; i += (int64_t)gridDim.x * 256)
+        if (ws.cls[i] == 2) ws.flag[canny_find(ws.label, (int32_t)i)] = 1;      // (every writer stores the same 1; read by launch 5)
+}
+
+// a thread per 4 consecutive pixels: whole dwords of the output where all four exist (dst is 4-byte aligned)
+__global__ __launch_bounds__(256) void canny_emit_kernel(const i2i_canny_u8_params p) {
+    const int64_t P = (int64_t)p.n * p.h * p.w;
+    const canny_ws ws = canny_carve(p.ws, P);
+    const int64_t groups = (P + 3) / 4;
+    uint8_t* dst = (uint8_t*)p.dst;
+    for (int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x; gi < groups; gi += (int64_t)gridDim.x * 256) {
+        const int64_t i0 = gi * 4;
+        uint32_t e[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t i = i0 + k;
+            e[k] = (i < P && ws.cls[i] != 0 && ws.flag[canny_find(ws.label, (int32_t)i)] != 0) ? 0xffu : 0u;
+        }
+        if (i0 + 4 <= P && p.out_c == 1) {
+            *(uint32_t*)(dst + i0) = e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24);
+        } else if (i0 + 4 <= P) {                            // out_c == 3: 12 bytes
+            uint32_t* d = (uint32_t*)(dst + i0 * 3);
+            d[0] = e[0] * 0x010101u | (e[1] << 24);
+            d[1] = e[1] * 0x0101u | (e[2] << 16) | (e[2] << 24);
+            d[2] = e[2] | (e[3] * 0x010101u << 8);
+        } else {
+            for (int k = 0; k < 4 && i0 + k < P; ++k)
+                for (int ch = 0; ch < p.out_c; ++ch) dst[(i0 + k) * p.out_c + ch] = (uint8_t)e[k];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t i2i_canny_ws_bytes(int n, int h, int w) {
+    if (n < 1 || h < 1 || w < 1) return 0;
+    const size_t P = (size_t)n * (size_t)h * (size_t)w;
+    return (P * 9 + 15) & ~(size_t)15;
+}
+
+extern "C" int i2i_canny_u8(const i2i_canny_u8_params* p, int dtype, void* stream) {
+    (void)dtype;
+    if (!p || !p->src || !p->dst || !p->ws) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: null pointer");
+    if (p->c < 1 || p->c > 4 || (p->out_c != 1 && p->out_c != 3) || p->n < 1 || p->h < 1 || p->w < 1)
+        return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: bad geometry (c 1..4, out_c 1 or 3, positive sizes)");
+    const int64_t P = (int64_t)p->n * p->h * p->w;
+    if (P > 0x7fffffff) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: more than 2^31 - 1 pixels in the batch (labels are 32-bit pixel indices)");
+    if (((uintptr_t)p->src | (uintptr_t)p->dst) & 3) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: image batches must be 4-byte aligned");
+    if ((uintptr_t)p->ws & 15) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: the workspace must be 16-byte aligned");
+    if ((uintptr_t)p->thr_dev & 3) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: thr_dev must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t tiles = (int64_t)p->n * ((p->h + CTH - 1) / CTH) * ((p->w + CTW - 1) / CTW);
+    auto blocks = [](int64_t total) { const int64_t b = (total + 255) / 256; return (unsigned)(b < 65536 ? b : 65536); };
+    const size_t lds_nms = CPH * CPW * 4 + 3 * CMH * CMW * 2, lds_lab = (CMH * CMW + 2) * 4;
+    hipLaunchKernelGGL(canny_nms_kernel, dim3((unsigned)tiles), dim3(256), lds_nms, s, *p);
+    hipLaunchKernelGGL(canny_label_kernel, dim3((unsigned)tiles), dim3(256), lds_lab, s, *p);
+    hipLaunchKernelGGL(canny_merge_kernel, dim3(blocks(P)), dim3(256), 0, s, *p);
+    hipLaunchKernelGGL(canny_flag_kernel, dim3(blocks(P)), dim3(256), 0, s, *p);
+    hipLaunchKernelGGL(canny_emit_kernel, dim3(blocks((P + 3) / 4)), dim3(256), 0, s, *p);
+    return i2i::check_launch("canny_u8");
 }

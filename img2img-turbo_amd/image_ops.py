@@ -1,8 +1,9 @@
 """Device-side image pre/post-processing of the callers (row f1): LANCZOS resize of uint8 HWC image batches, bit-identical to
-Pillow, which the reference applies on the host before and after the generator:
+Pillow, and Canny edge detection, both of which the reference applies on the host around the generator:
 
   src/inference_paired.py:38-41    input_image.resize((w - w % 8, h - h % 8), Image.LANCZOS)
   src/inference_unpaired.py:40,53  transforms.Resize((512, 512), LANCZOS) ... output_pil.resize(input size, Image.LANCZOS)
+  src/inference_paired.py:47-50    canny_from_pil(input_image, low, high) = cv2.Canny replicated to 3 channels (src/image_prep.py:6-12)
 
 The tap windows and 22-bit fixed-point weights are computed here in double precision exactly as Pillow's
 ``precompute_coeffs`` / ``normalize_coeffs_8bpc`` do (src/libImaging/Resample.c); the two integer passes run in
@@ -106,6 +107,35 @@ def lanczos_resize_u8(images, size, lib=None):
             lib.check(lib.lib.i2i_resize_u8(C.addressof(p), 0, stream))
             cur = out
     return cur
+
+
+def canny_thresholds(low, high):
+    """The two ints the kernels compare against: float thresholds floored (the magnitudes are integers, so ``mag > floor(t)`` is
+    ``mag > t``); the kernels swap them if low > high."""
+    return int(math.floor(low)), int(math.floor(high))
+
+
+def canny_u8(images, low=100, high=200, out_channels=3, lib=None):
+    """images: uint8 [N, H, W, C] (C <= 4) on the device -> uint8 [N, H, W, out_channels] (1 or 3), 255 on edges: ``cv2.Canny(img, low,
+    high)`` (aperture 3, L1 gradient) per image, replicated over the channels as ``canny_from_pil`` does (src/image_prep.py:6-12).  The
+    contract is spelled out at i2i_canny_u8_params (include/i2i_turbo.h), tests/canny_ref.py is its CPU oracle; parity with OpenCV itself is
+    unpinned where cv2 is not installed.  Asynchronous on the current stream (five launches in csrc/resize.hip, no read-back)."""
+    assert images.dtype == torch.uint8 and images.dim() == 4 and 1 <= images.shape[-1] <= 4
+    lib = lib or _capi.default_library()
+    n, h, w, c = images.shape
+    src = images.contiguous()
+    dev = src.device
+    assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+    lo, hi = canny_thresholds(low, high)
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        out = torch.empty((n, h, w, int(out_channels)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(lib.canny_ws_bytes(n, h, w), 16), dtype=torch.uint8, device=dev)
+        p = _capi.CannyU8Params()
+        p.src, p.dst, p.ws, p.thr_dev = src.data_ptr(), out.data_ptr(), ws.data_ptr(), 0
+        p.n, p.h, p.w, p.c, p.out_c, p.low, p.high = n, h, w, c, int(out_channels), lo, hi
+        lib.check(lib.lib.i2i_canny_u8(C.addressof(p), 0, stream))
+    return out
 
 
 def resize_to_multiple_of_8(images, lib=None):

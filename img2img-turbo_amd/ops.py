@@ -145,6 +145,16 @@ def nchw_to_nhwc(x, y, *, n, c, h, w, cpad, mul=1.0, add=0.0, binarize_below=0):
     return K.OP_NCHW_TO_NHWC, p
 
 
+def canny_u8(src, dst, ws, *, n, h, w, c, out_c=3, low=100, high=200, thr_dev=None):
+    """dst[n, h, w, out_c] = Canny edge map (255 / 0) of the uint8 HWC batch src[n, h, w, c]: cv2.Canny(img, low, high) replicated to out_c
+    channels (src/image_prep.py:6-12).  ``ws``: a uint8 tensor of at least Library.canny_ws_bytes(n, h, w) bytes; ``thr_dev``: optional int32
+    device tensor {low, high} read at run time instead of the two ints."""
+    p = K.CannyU8Params()
+    p.src, p.dst, p.ws, p.thr_dev = ptr(src), ptr(dst), ptr(ws), ptr(thr_dev)
+    p.n, p.h, p.w, p.c, p.out_c, p.low, p.high = n, h, w, c, out_c, int(low), int(high)
+    return K.OP_CANNY_U8, _keep(p, src, dst, ws, thr_dev)
+
+
 def nhwc_to_nchw(x, y, *, n, c, h, w, ldx, clamp=0, mul=0.0, add=0.0):
     """y: NCHW float tensor, or a uint8 HWC image batch [n, h, w, c] (then y = trunc(clamp01(x*mul+add)*255))."""
     p = K.NhwcToNchwParams()

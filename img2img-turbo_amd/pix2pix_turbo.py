@@ -152,21 +152,25 @@ class TurboGeneratorBase(torch.nn.Module):
                 for pk in self._packers.values():
                     pk.set_scale(r, r)
 
-    def get_plan(self, B, H, W, stochastic=False, r=1.0, direction="a2b", ctx_batch=1, u8_io=None) -> ForwardPlan:
+    def get_plan(self, B, H, W, stochastic=False, r=1.0, direction="a2b", ctx_batch=1, u8_io=None, canny=False) -> ForwardPlan:
         """The cached plan for this shape.  `r` is not part of the key (device addresses do not depend on it): ONE plan object
         per key, which records the r of the most recent get_plan() for that key and re-applies it whenever it runs
         (ForwardPlan.before_run).  Plans of DIFFERENT keys (a stochastic and a deterministic one, two sizes) can be held and
         interleaved safely; two r values for the SAME key are the same object -- the last get_plan() wins, so ask again
-        (it is a dictionary lookup) before running with another r."""
+        (it is a dictionary lookup) before running with another r.  ``canny=True`` (uint8 boundary only): the program starts with Canny
+        edge detection of "x"; only the boolean is part of the key -- the thresholds are device state of the plan
+        (ForwardPlan.set_canny_thresholds), so every (low, high) shares one plan and one captured graph."""
         r_plan = float(r) if stochastic else 1.0
         self.set_lora_scale(r_plan)
-        key = (B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io)
+        key = (B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((True,) if canny else ())
         if key in self._plans:
             self._plans.move_to_end(key)
         else:
             opts = dict(self.plan_options)
             if u8_io is not None:
                 opts["u8_io"] = u8_io
+            if canny:
+                opts["canny"] = True
             with self._on_device():
                 self._plans[key] = ForwardPlan(self.lib, self.weights, B, H, W, self.dtype_, self.device_, stochastic=stochastic,
                                                r=self._r, direction=direction, ctx_batch=ctx_batch, fuse_gn=self.fuse_gn,
@@ -206,9 +210,11 @@ class TurboGeneratorBase(torch.nn.Module):
         if noise_map is not None:
             plan.noise.copy_(noise_map.expand_as(plan.noise))
 
-    def _execute(self, plan: ForwardPlan, x, caption_enc, eps, noise_map=None):
+    def _execute(self, plan: ForwardPlan, x, caption_enc, eps, noise_map=None, canny=None):
         with self._on_device():
             self.stage(plan, x, caption_enc, eps, noise_map)
+            if canny is not None:
+                plan.set_canny_thresholds(*canny)
             if self.use_graph:
                 plan.replay()
             else:
@@ -242,23 +248,34 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
             self.lora_rank_unet, self.lora_rank_vae = weights.meta["rank_unet"], weights.meta["rank_vae"]
 
     @torch.no_grad()
-    def forward_u8(self, images_u8, *args, resize=None, sketch=False, **kw):
+    def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, **kw):
         """uint8 HWC in, uint8 HWC out ([B, H, W, 3] on the device): the callers' ``F.to_tensor`` (src/inference_paired.py:50)
         and ``ToPILImage()(out*0.5+0.5)`` (:72) run inside the boundary kernels; everything else as ``forward``.
         ``resize="multiple_of_8"`` first applies the script's ``input_image.resize((w - w % 8, h - h % 8), Image.LANCZOS)``
         (:38-41) on the device, bit-identical to Pillow (image_ops.lanczos_resize_u8); ``resize=(width, height)`` any size.
         ``sketch=True``: the sketch branch's binarisation ``F.to_tensor(input_image) < 0.5`` (:57-58) instead of ``to_tensor``
-        (bytes below 128 become 1.0, the others 0.0), as the stochastic sketch model expects."""
+        (bytes below 128 become 1.0, the others 0.0), as the stochastic sketch model expects.
+        ``canny=(low, high)`` or ``canny=True`` (100, 200): the edge_to_image branch, ``canny_from_pil(input_image, low, high)`` (:47-50 =
+        cv2.Canny replicated to 3 channels, src/image_prep.py:6-12), after the optional resize and in front of ``to_tensor`` -- the first op
+        of the planned program (csrc/resize.hip), so photo -> resize -> Canny -> generator -> uint8 image is one asynchronous sequence.
+        Every (low, high) runs the same plan / captured graph (the thresholds are device state).  OpenCV parity is unpinned where cv2 is
+        absent: tests/canny_ref.py is the oracle of the contract in include/i2i_turbo.h."""
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
+        if canny is not None and canny is not False:
+            if sketch:
+                raise ValueError("canny and sketch=True are the two exclusive branches of the script (src/inference_paired.py:47-58)")
+            canny = (100, 200) if canny is True else (canny[0], canny[1])
+        else:
+            canny = None
         if resize is not None:
             from .image_ops import lanczos_resize_u8, resize_to_multiple_of_8
             with self._on_device():
                 images_u8 = resize_to_multiple_of_8(images_u8, self.lib) if resize == "multiple_of_8" else lanczos_resize_u8(images_u8, resize, self.lib)
-        return self.forward(images_u8, *args, _u8_io=(1.0, 0.0, 128) if sketch else (1.0, 0.0), **kw)
+        return self.forward(images_u8, *args, _u8_io=(1.0, 0.0, 128) if sketch else (1.0, 0.0), _canny=canny, **kw)
 
     @torch.no_grad()
     def forward(self, c_t, prompt=None, prompt_tokens=None, deterministic=True, r=1.0, noise_map=None,
-                *, caption_enc=None, eps=None, _u8_io=None):
+                *, caption_enc=None, eps=None, _u8_io=None, _canny=None):
         if caption_enc is None:
             # either the prompt or the prompt_tokens should be provided (src/pix2pix_turbo.py:188)
             assert (prompt is None) != (prompt_tokens is None), "Either prompt or prompt_tokens should be provided"
@@ -279,8 +296,8 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
             torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
         ctx_batch = caption_enc.shape[0] if caption_enc.dim() == 3 else 1
         assert ctx_batch in (1, B)
-        plan = self.get_plan(B, H, W, stochastic=not deterministic, r=r, ctx_batch=ctx_batch, u8_io=_u8_io)
-        out = self._execute(plan, c_t, caption_enc, eps, None if deterministic else noise_map)
+        plan = self.get_plan(B, H, W, stochastic=not deterministic, r=r, ctx_batch=ctx_batch, u8_io=_u8_io, canny=_canny is not None)
+        out = self._execute(plan, c_t, caption_enc, eps, None if deterministic else noise_map, canny=_canny)
         if _u8_io is not None:
             return out
         return out.to(c_t.dtype) if c_t.dtype in (torch.float16, torch.bfloat16, torch.float32) else out

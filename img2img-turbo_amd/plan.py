@@ -75,7 +75,7 @@ class ForwardPlan:
 
     def __init__(self, lib, weights, B, H, W, dtype, device, *, stochastic=False, r=1.0, direction="a2b",
                  ctx_batch=1, fuse_gn=True, flash=True, out_dtype=None, packers=None, debug=False, dma_small=True, fuse_gn_stats=True, subpix=True, halo_min_tiles=160, u8_io=None, fuse_vae_attention=True,
-                 unet_dtype=None):
+                 unet_dtype=None, canny=False):
         assert H % 8 == 0 and W % 8 == 0, "input must be a multiple of 8 (src/inference_paired.py:38-41)"
         # H, W multiples of 8 suffice (src/inference_paired.py:38-41): latent sizes that are not multiples of 8 make the
         # UNet levels odd (70 -> 35 -> 18 -> 9), handled like diffusers' forward_upsample_size path (explicit sizes).
@@ -151,6 +151,15 @@ class ForwardPlan:
         # (row f1: F.to_tensor / Normalize / x*0.5+0.5 / ToPILImage of the callers run inside the boundary kernels)
         self.u8_io = u8_io
         self.ctx_batch = ctx_batch
+        # canny: the program starts with Canny edge detection of x_in (the edge_to_image script's canny_from_pil, src/inference_paired.py:47-50;
+        # csrc/resize.hip): x_in holds the photos, the boundary op reads the plan-owned edge maps.  The thresholds are DEVICE state
+        # (canny_thr = {low, high}, read by the kernels at run time), so the program, its hipGraph and an exported plan file follow the
+        # caller's sliders without re-planning.
+        self.canny = bool(canny)
+        assert not self.canny or u8_io, "canny needs the uint8 boundary (u8_io)"
+        self.canny_thr = torch.tensor([100, 200], dtype=torch.int32, device=device) if self.canny else None
+        self.canny_edges = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if self.canny else None
+        self.canny_ws = torch.zeros(max(lib.canny_ws_bytes(B, H, W), 16), dtype=torch.uint8, device=device) if self.canny else None
         self.x_in = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
                      torch.zeros(B, 3, H, W, dtype=torch.float32, device=device))
         self.eps = torch.zeros(B, lat, h8, w8, dtype=torch.float32, device=device)
@@ -969,7 +978,12 @@ class ForwardPlan:
         self._zero_init = []
         x = self.new(B, H, W, 8)
         mul, add, thr = (tuple(self.u8_io) + (0,))[:3] if self.u8_io else (1.0, 0.0, 0)      # (mul, add[, binarize_below])
-        self._add(O.nchw_to_nhwc(self.x_in, x.t, n=B, c=3, h=H, w=W, cpad=8, mul=mul, add=add, binarize_below=thr), "input.to_nhwc",
+        src = self.x_in
+        if self.canny:
+            self._add(O.canny_u8(self.x_in, self.canny_edges, self.canny_ws, n=B, h=H, w=W, c=3, out_c=3, thr_dev=self.canny_thr), "input.canny",
+                      nbytes=B * H * W * 6)
+            src = self.canny_edges
+        self._add(O.nchw_to_nhwc(src, x.t, n=B, c=3, h=H, w=W, cpad=8, mul=mul, add=add, binarize_below=thr), "input.to_nhwc",
                   nbytes=B * H * W * (3 * self.x_in.element_size() + 8 * self.esz))
         moments, skips = self._vae_encoder(x)
         # x (= conv_in input) is not a skip; skips[0] is conv_in's output
@@ -1014,6 +1028,14 @@ class ForwardPlan:
     # single-stream with respect to r: the re-merge rewrites the weights in place on the current stream.
     before_run = None
     released = False
+
+    def set_canny_thresholds(self, low, high):
+        """Write the Canny thresholds the next run / replay uses (floats are floored; asynchronous on the current stream)."""
+        assert self.canny, "this plan has no Canny op (get_plan(..., canny=True))"
+        from .image_ops import canny_thresholds
+        lo, hi = canny_thresholds(low, high)
+        self.canny_thr[0:1].fill_(lo)          # (fill kernels: the values travel as launch arguments, no host buffer to keep alive)
+        self.canny_thr[1:2].fill_(hi)
 
     def _prepare(self):
         if self.released:

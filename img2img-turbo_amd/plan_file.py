@@ -11,7 +11,8 @@ What is saved: the op program (``plan.prog``: every launch with its tile / route
 torch storage an op pointer refers to, and a relocation table (op, pointer field) -> (buffer, offset).  Buffers of the plan's
 recycling pool and its boundary buffers are *scratch* (size only, zero-filled at load); everything else -- packed weights with the LoRA
 merged at the current scale, norm parameters, device scalars, ticket counters -- is saved with its contents.  The boundary buffers get
-names: "x", "ctx", "eps", "noise" (stochastic plans), "out".
+names: "x", "ctx", "eps", "noise" (stochastic plans), "out", and "canny_thr" (plans with the Canny op in front: two int32 {low, high},
+saved with the values of the export, which a host overwrites with i2i_plan_write to move the thresholds).
 
 This replaces the reference's ``model(...)`` call (src/pix2pix_turbo.py:186-219, src/cyclegan_turbo.py:241-254) for hosts that are not
 Python; the planner itself (route queries, tile choices, buffer recycling) stays in plan.py and runs once, at export.
@@ -55,8 +56,12 @@ def export_plan(plan, path, extra_tensors=()):
         named["noise"] = plan.noise
     # (the GroupNorm scratch -- partial sums, (scale, shift) tables, ticket counters -- is patched into the ops after they were recorded:
     # plan._finish_gn_scratch; produced inside the program, zero at rest)
+    if getattr(plan, "canny", False):
+        named["canny_thr"] = plan.canny_thr
     gn_scratch = [t for t in (getattr(plan, n, None) for n in ("gn_partial", "gn_ss", "gn_counters")) if t is not None]
-    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, holders=[plan] + list(extra_tensors), device=plan.device)
+    if getattr(plan, "canny", False):
+        gn_scratch += [plan.canny_edges, plan.canny_ws]
+    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr",), holders=[plan] + list(extra_tensors), device=plan.device)
 
 
 def export_text_plan(encoder, batch, path):
@@ -70,12 +75,13 @@ def export_text_plan(encoder, batch, path):
     return export_program(tp.prog, path, {"ids": tp.ids, "ctx": tp.out}, scratch=list(tp._keep), holders=[tp, encoder.w], device=encoder.device)
 
 
-def export_program(prog, path, named, scratch=(), holders=(), device="cpu"):
+def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep_contents=()):
     """The file writer behind both: ``prog`` (a frozen _capi.Program), ``named`` boundary tensors, ``scratch`` tensors whose contents need
-    not be saved (zero-filled at load, like the boundary buffers), ``holders``: objects / tensors that own anything else the ops point at."""
+    not be saved (zero-filled at load, like the boundary buffers), ``holders``: objects / tensors that own anything else the ops point at,
+    ``keep_contents``: names of boundary tensors that are saved WITH their contents (parameters with a meaningful default)."""
     assert prog.array is not None, "the program is not frozen"
     named = dict(named)
-    scratch_keys = {_storage_key(t) for t in list(scratch) + list(named.values())}
+    scratch_keys = {_storage_key(t) for t in list(scratch) + [t for n, t in named.items() if n not in keep_contents]}
     tensors = list(named.values()) + list(scratch)
 
     def harvest(obj, depth):                     # any other tensor the plan (or its packers) holds -- device scalars such as the LoRA /
@@ -160,7 +166,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu"):
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--direction a2b] [--u8] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--direction a2b] [--u8 [--canny LOW HIGH]] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -175,6 +181,9 @@ def main(argv=None):
                     "script does (F.to_tensor(img) < 0.5, src/inference_paired.py:56-58); implied by --stochastic --u8")
     ap.add_argument("--direction", default="a2b", choices=["a2b", "b2a"])
     ap.add_argument("--u8", action="store_true", help="uint8 NHWC boundary (to_tensor / Normalize / ToPILImage inside the boundary kernels)")
+    ap.add_argument("--canny", type=float, nargs=2, default=None, metavar=("LOW", "HIGH"), help="with --u8 (pix2pix): 'x' holds photos; the program "
+                    "starts with Canny edge detection (canny_from_pil, src/inference_paired.py:47-50).  LOW HIGH are the thresholds saved in the file; "
+                    "a host moves them by writing two int32 to the buffer named 'canny_thr'")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--base-dir", default=None, help="local stabilityai/sd-turbo snapshot directory")
     ap.add_argument("--pretrained-path", default=None, help="the reference's LoRA checkpoint (.pkl)")
@@ -183,6 +192,8 @@ def main(argv=None):
     ap.add_argument("--lib", default=None, help="another build of the kernel library (tests: the CPU emulator)")
     a = ap.parse_args(argv)
     dt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[a.dtype]
+    if a.canny is not None and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
+        ap.error("--canny requires --u8 on a deterministic pix2pix plan (the edge_to_image branch; not with --sketch / --stochastic)")
     H, W = a.size[0], a.size[-1]
     kw = dict(device=a.device, dtype=dt)
     if a.lib:
@@ -208,7 +219,9 @@ def main(argv=None):
         # `F.to_tensor(img) < 0.5`), which is what Pix2Pix_Turbo.forward_u8(..., sketch=True) feeds -- a stochastic plan is the sketch model
         u8 = ((1.0, 0.0, 128) if (a.sketch or a.stochastic) else (1.0, 0.0)) if a.u8 else None
         gamma = a.gamma if a.gamma is not None else (0.4 if a.stochastic else 1.0)
-        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8)
+        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=a.canny is not None)
+        if a.canny is not None:
+            plan.set_canny_thresholds(*a.canny)
     info = export_plan(plan, a.out)                 # (re-merges the weights at this plan's r first: plan._prepare)
     print("wrote %s: %d ops, %d buffers, %.2f GB of weights, %.2f GB of scratch at load; boundary buffers %s"
           % (a.out, info["ops"], info["buffers"], info["data_bytes"] / 1e9, info["scratch_bytes"] / 1e9, info["io"]))

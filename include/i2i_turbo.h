@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define I2I_ABI_VERSION 10
+#define I2I_ABI_VERSION 11
 
 typedef enum { I2I_F32 = 0, I2I_BF16 = 1, I2I_F16 = 2,
                I2I_U8 = 3   /* only as src_dtype / dst_dtype of the boundary layout ops: uint8 images, HWC interleaved */
@@ -52,7 +52,8 @@ typedef enum {
     I2I_OP_EMBED = 11,
     I2I_OP_LORA_MERGE = 12,
     I2I_OP_RESIZE_U8 = 13,
-    I2I_OP_NOP = 14            /* one empty kernel launch (bench.py's calibration: microseconds per hipGraph node) */
+    I2I_OP_NOP = 14,           /* one empty kernel launch (bench.py's calibration: microseconds per hipGraph node) */
+    I2I_OP_CANNY_U8 = 15
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -278,6 +279,28 @@ typedef struct {
     const int32_t* bounds; const int32_t* coeffs;
 } i2i_resize_u8_params;
 
+/* Canny edge detection on uint8 HWC image batches (ABI v11): cv::Canny(src, low, high) for 8-bit input with aperture 3 and
+ * L2gradient = false, restated in integer arithmetic, replicated to out_c channels -- the reference's host-side
+ * canny_from_pil (src/image_prep.py:6-12: cv2.Canny + the 3-channel replication) between the resize and F.to_tensor of the
+ * edge_to_image script (src/inference_paired.py:47-50).  Per pixel:
+ *   1. 3x3 Sobel dx, dy per channel (BORDER_REPLICATE);  2. mag = |dx| + |dy|, the pixel takes (dx, dy, mag) of the channel with the
+ *   largest mag (lowest channel on a tie);  3. non-maximum suppression along the gradient direction quantised to 0 / 45 / 90 / 135
+ *   degrees with the integer tangents tan(22.5) = 13573 / 2^15, mag outside the image = 0: a surviving pixel with mag > low is a
+ *   candidate, strong if mag > high;  4. hysteresis: a candidate is an edge iff its 8-connected component of candidates holds a
+ *   strong pixel;  5. dst = 255 on edges, 0 elsewhere.
+ * The result is a pure function of the input (bit-identical from run to run; tests/canny_ref.py is the CPU oracle of this text).
+ * Parity with OpenCV itself is unpinned where cv2 is absent (tests/test_canny_emu.py pins it where cv2 imports).
+ * Five launches whatever the image holds (class map, tile-local labels, lock-free union of the tile roots across tile edges, strong
+ * flags, output); no read-back, no grid-wide wait.  `ws` is state of the run in flight (see the CONCURRENCY note of i2i_gn_stats_params). */
+typedef struct {
+    const void* src; void* dst;        /* uint8 [n][h][w][c] -> uint8 [n][h][w][out_c]; 4-byte aligned */
+    int32_t n, h, w, c, out_c;         /* c 1..4; out_c 1 or 3 */
+    int32_t low, high;                 /* swapped if low > high */
+    const int32_t* thr_dev;            /* optional device {low, high} read at run time: a captured graph / loaded plan stays valid
+                                          when the caller moves the sliders (gradio_canny2image.py), like posterior.r_dev */
+    void* ws;                          /* >= i2i_canny_ws_bytes(n, h, w) bytes, 16-byte aligned; contents irrelevant before and after */
+} i2i_canny_u8_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -298,6 +321,7 @@ typedef struct {
         i2i_lora_merge_params lora_merge;
         i2i_resize_u8_params resize_u8;
         i2i_nop_params nop;
+        i2i_canny_u8_params canny_u8;
     } u;
 } i2i_op;
 
@@ -328,6 +352,8 @@ int i2i_ddpm_postquant(const i2i_ddpm_params* p, int dtype, void* stream);
 int i2i_embed(const i2i_embed_params* p, int dtype, void* stream);
 int i2i_lora_merge(const i2i_lora_merge_params* p, int dtype, void* stream);
 int i2i_resize_u8(const i2i_resize_u8_params* p, int dtype, void* stream);   /* dtype ignored (uint8 data) */
+int i2i_canny_u8(const i2i_canny_u8_params* p, int dtype, void* stream);     /* dtype ignored (uint8 data); five launches */
+size_t i2i_canny_ws_bytes(int n, int h, int w);                              /* bytes of i2i_canny_u8_params.ws (0 for a non-positive size) */
 
 /* ---- calibration micro-kernels (csrc/calib.hip; bench.py's `calib` block: what THIS box delivers on three elementary loads, so that
  * lines measured on different boxes of a pool can be compared).  Not on the forward path. */
