@@ -1,7 +1,8 @@
 // Boundary and latent-space elementwise kernels for gfx950 (all HBM-bound, one thread per pixel):
 //   NCHW <-> NHWC conversion at the .forward() boundary (torch callers hand NCHW; the kernels run NHWC),
 //   DiagonalGaussianDistribution.sample()*scaling_factor + the stochastic mix (src/pix2pix_turbo.py:198,210),
-//   DDPMScheduler.step + /scaling_factor + post_quant_conv (src/pix2pix_turbo.py:200-203).
+//   DDPMScheduler.step + /scaling_factor + post_quant_conv (src/pix2pix_turbo.py:200-203),
+//   the seeded Gaussian noise of the callers (torch.manual_seed + torch.randn, src/inference_paired.py:58-60): Philox4x32-10 + Box-Muller.
 #include "i2i_dev.h"
 #include "launch.h"
 
@@ -138,6 +139,60 @@ __global__ __launch_bounds__(256) void ddpm_kernel(const i2i_ddpm_params p) {
     }
 }
 
+// ---- seeded noise (the contract is the comment of i2i_randn_params): one thread per Philox counter = four consecutive elements
+__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = umulhi_u32(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = umulhi_u32(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const u32x4 nx = {hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0};
+        c = nx;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
+// words (wa, wb) -> two normal deviates; u1 in (0, 1] and 2*u2 in [0, 2) are exact in fp32, the functions are the precise ones
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, uint32_t& x, uint32_t& y) {
+    const float u1 = (float)((wa >> 8) + 1u) * 0x1p-24f;
+    const float t = (float)(wb >> 8) * 0x1p-23f;
+    const float rad = sqrtf(-2.0f * logf(u1));
+    x = __builtin_bit_cast(uint32_t, rad * cospi_f(t));
+    y = __builtin_bit_cast(uint32_t, rad * sinpi_f(t));
+}
+
+template <bool NORMAL>
+__global__ __launch_bounds__(256) void randn_kernel(const i2i_randn_params p) {
+    const uint32_t k0 = p.state ? p.state[0] : (uint32_t)p.seed, k1 = p.state ? p.state[1] : (uint32_t)(p.seed >> 32);
+    const uint32_t step = p.state ? p.state[2] : p.step;
+    uint32_t* dst = (uint32_t*)p.dst;
+    const bool wide = ((uintptr_t)dst & 15) == 0;          // dst + 4q is then 16-byte aligned for every q
+    const int64_t nq = (p.n + 3) >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
+        const u32x4 ctr = {(uint32_t)q, (uint32_t)((uint64_t)q >> 32), step, p.stream_id};
+        u32x4 w = philox4x32_10(ctr, k0, k1);
+        if (NORMAL) {
+            uint32_t a, b, c, d;
+            box_muller(w[0], w[1], a, b);
+            box_muller(w[2], w[3], c, d);
+            const u32x4 g = {a, b, c, d};
+            w = g;
+        }
+        const int64_t i = q << 2;
+        if (wide && i + 4 <= p.n) {
+            *(u32x4*)(dst + i) = w;
+        } else {
+            for (int e = 0; e < 4; ++e)
+                if (i + e < p.n) dst[i + e] = w[e];
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void randn_advance_kernel(uint32_t* state) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) state[2] += 1u;
+}
+
 inline unsigned grid_for(int64_t n) {
     const int64_t b = (n + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -244,4 +299,24 @@ extern "C" int i2i_embed(const i2i_embed_params* p, int dtype, void* stream) {
         default: return i2i::fail(I2I_ERR_BAD_ARG, "embed: bad dtype");
     }
     return i2i::check_launch("embed");
+}
+
+extern "C" int i2i_randn(const i2i_randn_params* p, int /*dtype*/, void* stream) {
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "randn: null params");
+    hipStream_t s = (hipStream_t)stream;
+    if (p->kind == I2I_RANDN_ADVANCE) {
+        if (!p->state) return i2i::fail(I2I_ERR_BAD_ARG, "randn: advance needs the device state");
+        hipLaunchKernelGGL(randn_advance_kernel, dim3(1), dim3(64), 0, s, (uint32_t*)p->state);
+        return i2i::check_launch("randn_advance");
+    }
+    if (p->kind != I2I_RANDN_NORMAL && p->kind != I2I_RANDN_RAW) return i2i::fail(I2I_ERR_BAD_ARG, "randn: unknown kind %d", p->kind);
+    if (p->n < 0) return i2i::fail(I2I_ERR_BAD_ARG, "randn: n = %lld < 0", (long long)p->n);
+    if (p->n == 0) return I2I_OK;
+    if (!p->dst || ((uintptr_t)p->dst & 3)) return i2i::fail(I2I_ERR_BAD_ARG, "randn: dst is null or not 4-byte aligned");
+    // at most 1024 workgroups (4 per CU): 2^18 counters = 2^20 elements per pass of the grid-stride loop
+    const int64_t b = (((p->n + 3) >> 2) + 255) / 256;
+    const unsigned g = (unsigned)(b > 1024 ? 1024 : b);
+    if (p->kind == I2I_RANDN_NORMAL) hipLaunchKernelGGL((randn_kernel<true>), dim3(g), dim3(256), 0, s, *p);
+    else hipLaunchKernelGGL((randn_kernel<false>), dim3(g), dim3(256), 0, s, *p);
+    return i2i::check_launch("randn");
 }

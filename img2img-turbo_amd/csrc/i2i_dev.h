@@ -140,6 +140,29 @@ __device__ __forceinline__ int32_t agent_load_i32(const int32_t* p) { return __h
 __device__ __forceinline__ int32_t agent_min_i32(int32_t* p, int32_t v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
 
+// ---- arithmetic of the seeded noise op (randn_kernel, elementwise.hip): the high half of a 32 x 32 bit product (v_mul_hi_u32) and the
+// pi-scaled trigonometric functions (exact argument reduction: no fp32 product with pi).  The host has neither: the emulator reduces
+// the argument (in [0, 2)) to a multiple of 1/2 plus |r| <= 1/4 exactly and evaluates in double, well inside the 1 ulp of the device's.
+#ifdef I2I_EMU
+__device__ __forceinline__ uint32_t umulhi_u32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+__device__ __forceinline__ void emu_sincospi(float x, double& s, double& c) {
+    const int k = (int)nearbyint(2.0 * (double)x);
+    const double r = 3.14159265358979323846 * ((double)x - 0.5 * k), sr = sin(r), cr = cos(r);
+    switch (k & 3) {
+        case 0: s = sr; c = cr; break;
+        case 1: s = cr; c = -sr; break;
+        case 2: s = -sr; c = -cr; break;
+        default: s = -cr; c = sr; break;
+    }
+}
+__device__ __forceinline__ float cospi_f(float x) { double s, c; emu_sincospi(x, s, c); return (float)c; }
+__device__ __forceinline__ float sinpi_f(float x) { double s, c; emu_sincospi(x, s, c); return (float)s; }
+#else
+__device__ __forceinline__ uint32_t umulhi_u32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+__device__ __forceinline__ float cospi_f(float x) { return cospif(x); }
+__device__ __forceinline__ float sinpi_f(float x) { return sinpif(x); }
+#endif
+
 // ---- explicit synchronisation for LDS-DMA pipelines (cdna_hip_programming.md section 5: raw s_barrier +
 // counted waits; __syncthreads() would drain the DMA queue with vmcnt(0) at every barrier).
 // The CPU emulator (tests/emu, I2I_EMU) executes copies synchronously, so the waits are no-ops there.

@@ -80,6 +80,7 @@ const std::vector<size_t>& ptr_fields(int opcode) {
                                              PF(lora_merge, kscale), PF(lora_merge, kshift), PF(lora_merge, bias0), PF(lora_merge, colsum), PF(lora_merge, bias_out)};
     static const std::vector<size_t> resize = {PF(resize_u8, src), PF(resize_u8, dst), PF(resize_u8, bounds), PF(resize_u8, coeffs)};
     static const std::vector<size_t> canny = {PF(canny_u8, src), PF(canny_u8, dst), PF(canny_u8, thr_dev), PF(canny_u8, ws)};
+    static const std::vector<size_t> randn = {PF(randn, dst), PF(randn, state)};
     switch (opcode) {
         case I2I_OP_IGEMM: return igemm;
         case I2I_OP_GN_STATS: return gn_stats;
@@ -95,6 +96,7 @@ const std::vector<size_t>& ptr_fields(int opcode) {
         case I2I_OP_LORA_MERGE: return lora;
         case I2I_OP_RESIZE_U8: return resize;
         case I2I_OP_CANNY_U8: return canny;
+        case I2I_OP_RANDN: return randn;
         default: return none;
     }
 }

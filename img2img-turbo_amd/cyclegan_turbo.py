@@ -51,7 +51,7 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         ``ToPILImage()(out*0.5+0.5)`` (:53) run inside the boundary kernels.  ``resize=(width, height)`` applies the script's
         ``transforms.Resize(..., LANCZOS)`` (:40-47, e.g. (512, 512) for "resize_512x512") before the generator and
         ``resize_back=True`` its ``output_pil.resize((input width, input height), Image.LANCZOS)`` (:53) after it, both on the
-        device and bit-identical to Pillow (image_ops.lanczos_resize_u8)."""
+        device and bit-identical to Pillow (image_ops.lanczos_resize_u8).  ``seed=``: as in ``forward``."""
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
         in_hw = images_u8.shape[1:3]
         if image_prep is not None:          # the script's build_transform(args.image_prep) (src/inference_unpaired.py:40, default "resize_512x512")
@@ -87,7 +87,11 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         return model.forward(x, direction=direction, caption_emb=text_emb, eps=eps)
 
     @torch.no_grad()
-    def forward(self, x_t, direction=None, caption=None, caption_emb=None, *, eps=None, _u8_io=None):
+    def forward(self, x_t, direction=None, caption=None, caption_emb=None, *, eps=None, seed=None, _u8_io=None):
+        """``seed=s``: the posterior draw comes from the device at (seed s, step 0) under the contract of i2i_randn_params
+        (include/i2i_turbo.h; img2img_turbo_amd.rng) instead of a host-side ``torch.randn``; not together with ``eps=``."""
+        if seed is not None and eps is not None:
+            raise ValueError("seed= draws eps on the device: do not pass eps= with it")
         if direction is None:
             assert self.direction is not None
             direction = self.direction
@@ -101,10 +105,10 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         else:
             B, _, H, W = x_t.shape
         lat = self.weights.vae_arch.latent_channels
-        if eps is None:
+        if eps is None and seed is None:
             eps = torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
             torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
         ctx_batch = caption_enc.shape[0] if caption_enc.dim() == 3 else 1
-        plan = self.get_plan(B, H, W, direction=direction, ctx_batch=ctx_batch, u8_io=_u8_io)
-        out = self._execute(plan, x_t, caption_enc, eps)
+        plan = self.get_plan(B, H, W, direction=direction, ctx_batch=ctx_batch, u8_io=_u8_io, rng=seed is not None)
+        out = self._execute(plan, x_t, caption_enc, eps, seed=seed)
         return out if _u8_io is not None else out.to(x_t.dtype)

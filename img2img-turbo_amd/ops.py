@@ -155,6 +155,17 @@ def canny_u8(src, dst, ws, *, n, h, w, c, out_c=3, low=100, high=200, thr_dev=No
     return K.OP_CANNY_U8, _keep(p, src, dst, ws, thr_dev)
 
 
+def randn(dst, *, n=None, state=None, seed=0, step=0, stream_id=0, kind=K.RANDN_NORMAL):
+    """dst[0 .. n-1] = seeded noise (the contract: i2i_randn_params, include/i2i_turbo.h): fp32 normal deviates (RANDN_NORMAL) or the raw
+    Philox words (RANDN_RAW, dst of a 4-byte integer type); RANDN_ADVANCE (dst = None) bumps the step word of ``state``.  ``state``:
+    optional 4-word device tensor {seed_lo, seed_hi, step, reserved} read at run time instead of the immediate seed / step."""
+    p = K.RandnParams()
+    p.dst, p.state = ptr(dst), ptr(state)
+    p.n = (dst.numel() if dst is not None else 0) if n is None else int(n)
+    p.seed, p.step, p.stream_id, p.kind = int(seed) & (2 ** 64 - 1), int(step) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF, int(kind)
+    return K.OP_RANDN, _keep(p, dst, state)
+
+
 def nhwc_to_nchw(x, y, *, n, c, h, w, ldx, clamp=0, mul=0.0, add=0.0):
     """y: NCHW float tensor, or a uint8 HWC image batch [n, h, w, c] (then y = trunc(clamp01(x*mul+add)*255))."""
     p = K.NhwcToNchwParams()

@@ -152,17 +152,19 @@ class TurboGeneratorBase(torch.nn.Module):
                 for pk in self._packers.values():
                     pk.set_scale(r, r)
 
-    def get_plan(self, B, H, W, stochastic=False, r=1.0, direction="a2b", ctx_batch=1, u8_io=None, canny=False) -> ForwardPlan:
+    def get_plan(self, B, H, W, stochastic=False, r=1.0, direction="a2b", ctx_batch=1, u8_io=None, canny=False, rng=False) -> ForwardPlan:
         """The cached plan for this shape.  `r` is not part of the key (device addresses do not depend on it): ONE plan object
         per key, which records the r of the most recent get_plan() for that key and re-applies it whenever it runs
         (ForwardPlan.before_run).  Plans of DIFFERENT keys (a stochastic and a deterministic one, two sizes) can be held and
         interleaved safely; two r values for the SAME key are the same object -- the last get_plan() wins, so ask again
         (it is a dictionary lookup) before running with another r.  ``canny=True`` (uint8 boundary only): the program starts with Canny
         edge detection of "x"; only the boolean is part of the key -- the thresholds are device state of the plan
-        (ForwardPlan.set_canny_thresholds), so every (low, high) shares one plan and one captured graph."""
+        (ForwardPlan.set_canny_thresholds), so every (low, high) shares one plan and one captured graph.  ``rng=True``: the program draws
+        "eps" (and "noise") itself from the plan's device state (ForwardPlan.set_seed; the contract of i2i_randn_params) and advances the step
+        after every run; again only the boolean is part of the key, every seed shares the plan."""
         r_plan = float(r) if stochastic else 1.0
         self.set_lora_scale(r_plan)
-        key = (B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((True,) if canny else ())
+        key = (B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((True,) if canny else ()) + (("rng",) if rng else ())
         if key in self._plans:
             self._plans.move_to_end(key)
         else:
@@ -171,6 +173,8 @@ class TurboGeneratorBase(torch.nn.Module):
                 opts["u8_io"] = u8_io
             if canny:
                 opts["canny"] = True
+            if rng:
+                opts["rng"] = True
             with self._on_device():
                 self._plans[key] = ForwardPlan(self.lib, self.weights, B, H, W, self.dtype_, self.device_, stochastic=stochastic,
                                                r=self._r, direction=direction, ctx_batch=ctx_batch, fuse_gn=self.fuse_gn,
@@ -203,16 +207,20 @@ class TurboGeneratorBase(torch.nn.Module):
         return self.text_encoder(ids.to(self.device_))[0].detach()
 
     def stage(self, plan: ForwardPlan, x, caption_enc, eps, noise_map=None):
-        """Copy one batch into the plan's static boundary buffers (device-to-device when the inputs are already resident)."""
+        """Copy one batch into the plan's static boundary buffers (device-to-device when the inputs are already resident).  ``eps=None``:
+        the plan draws its own noise (rng plans)."""
         plan.x_in.copy_(x)
         plan.ctx.copy_(caption_enc.reshape(plan.ctx.shape))
-        plan.eps.copy_(eps)
+        if eps is not None:
+            plan.eps.copy_(eps)
         if noise_map is not None:
             plan.noise.copy_(noise_map.expand_as(plan.noise))
 
-    def _execute(self, plan: ForwardPlan, x, caption_enc, eps, noise_map=None, canny=None):
+    def _execute(self, plan: ForwardPlan, x, caption_enc, eps, noise_map=None, canny=None, seed=None):
         with self._on_device():
             self.stage(plan, x, caption_enc, eps, noise_map)
+            if seed is not None:
+                plan.set_seed(seed, 0)
             if canny is not None:
                 plan.set_canny_thresholds(*canny)
             if self.use_graph:
@@ -259,7 +267,8 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         cv2.Canny replicated to 3 channels, src/image_prep.py:6-12), after the optional resize and in front of ``to_tensor`` -- the first op
         of the planned program (csrc/resize.hip), so photo -> resize -> Canny -> generator -> uint8 image is one asynchronous sequence.
         Every (low, high) runs the same plan / captured graph (the thresholds are device state).  OpenCV parity is unpinned where cv2 is
-        absent: tests/canny_ref.py is the oracle of the contract in include/i2i_turbo.h."""
+        absent: tests/canny_ref.py is the oracle of the contract in include/i2i_turbo.h.
+        ``seed=``: as in ``forward``."""
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
         if canny is not None and canny is not False:
             if sketch:
@@ -275,7 +284,13 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
 
     @torch.no_grad()
     def forward(self, c_t, prompt=None, prompt_tokens=None, deterministic=True, r=1.0, noise_map=None,
-                *, caption_enc=None, eps=None, _u8_io=None, _canny=None):
+                *, caption_enc=None, eps=None, seed=None, _u8_io=None, _canny=None):
+        """``seed=s``: the scripts' ``torch.manual_seed(s)`` + ``torch.randn`` (src/inference_paired.py:58-60) on the device -- the planned
+        program draws "eps" (and, stochastic, the noise map) itself at (seed s, step 0) under the contract of i2i_randn_params
+        (include/i2i_turbo.h; img2img_turbo_amd.rng): nothing is staged by the host, the same seed gives the same image on every call, and
+        ``noise_map`` is not needed.  Not together with ``eps=`` / ``noise_map=``.  ``seed=None``: as before."""
+        if seed is not None and (eps is not None or noise_map is not None):
+            raise ValueError("seed= draws eps and the noise map on the device: do not pass eps= / noise_map= with it")
         if caption_enc is None:
             # either the prompt or the prompt_tokens should be provided (src/pix2pix_turbo.py:188)
             assert (prompt is None) != (prompt_tokens is None), "Either prompt or prompt_tokens should be provided"
@@ -285,19 +300,20 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         else:
             B, _, H, W = c_t.shape
         if not deterministic:
-            if noise_map is None:
-                raise ValueError("stochastic forward needs noise_map (src/pix2pix_turbo.py:210)")
+            if noise_map is None and seed is None:
+                raise ValueError("stochastic forward needs noise_map (src/pix2pix_turbo.py:210) or seed=")
         elif self.weights.is_twin_conv:
             raise ValueError("this checkpoint wraps conv_in in a TwinConv, which the reference can only run with "
                              "deterministic=False (TwinConv.r is None otherwise, src/pix2pix_turbo.py:21-26)")
         lat = self.weights.vae_arch.latent_channels
-        if eps is None:   # latent_dist.sample() draw, then the (numerically dead) scheduler draw: same order as the reference
+        if eps is None and seed is None:   # latent_dist.sample() draw, then the (numerically dead) scheduler draw: same order as the reference
             eps = torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
             torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
         ctx_batch = caption_enc.shape[0] if caption_enc.dim() == 3 else 1
         assert ctx_batch in (1, B)
-        plan = self.get_plan(B, H, W, stochastic=not deterministic, r=r, ctx_batch=ctx_batch, u8_io=_u8_io, canny=_canny is not None)
-        out = self._execute(plan, c_t, caption_enc, eps, None if deterministic else noise_map, canny=_canny)
+        plan = self.get_plan(B, H, W, stochastic=not deterministic, r=r, ctx_batch=ctx_batch, u8_io=_u8_io, canny=_canny is not None,
+                             rng=seed is not None)
+        out = self._execute(plan, c_t, caption_enc, eps, None if deterministic else noise_map, canny=_canny, seed=seed)
         if _u8_io is not None:
             return out
         return out.to(c_t.dtype) if c_t.dtype in (torch.float16, torch.bfloat16, torch.float32) else out

@@ -75,7 +75,7 @@ class ForwardPlan:
 
     def __init__(self, lib, weights, B, H, W, dtype, device, *, stochastic=False, r=1.0, direction="a2b",
                  ctx_batch=1, fuse_gn=True, flash=True, out_dtype=None, packers=None, debug=False, dma_small=True, fuse_gn_stats=True, subpix=True, halo_min_tiles=160, u8_io=None, fuse_vae_attention=True,
-                 unet_dtype=None, canny=False):
+                 unet_dtype=None, canny=False, rng=False):
         assert H % 8 == 0 and W % 8 == 0, "input must be a multiple of 8 (src/inference_paired.py:38-41)"
         # H, W multiples of 8 suffice (src/inference_paired.py:38-41): latent sizes that are not multiples of 8 make the
         # UNet levels odd (70 -> 35 -> 18 -> 9), handled like diffusers' forward_upsample_size path (explicit sizes).
@@ -164,6 +164,12 @@ class ForwardPlan:
                      torch.zeros(B, 3, H, W, dtype=torch.float32, device=device))
         self.eps = torch.zeros(B, lat, h8, w8, dtype=torch.float32, device=device)
         self.noise = torch.zeros(B, lat, h8, w8, dtype=torch.float32, device=device) if stochastic else None
+        # rng: the program fills eps (and noise) itself -- seeded noise under the contract of i2i_randn_params (include/i2i_turbo.h), streams 0 and
+        # 2 -- from the DEVICE state rng_state = {seed_lo, seed_hi, step, reserved} (uint32 bits in an int32 tensor), and ends by advancing
+        # the step: the callers' torch.manual_seed(seed) + torch.randn (src/inference_paired.py:58-60) with one program, one hipGraph and one
+        # plan file for every seed, and fresh noise per replay without the host.
+        self.rng = bool(rng)
+        self.rng_state = torch.zeros(4, dtype=torch.int32, device=device) if self.rng else None
         self.ctx = torch.zeros(ctx_batch, 77, self.ua.cross_attention_dim, dtype=self.unet_dtype, device=device)
         self.out = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
                     torch.zeros(B, 3, H, W, dtype=self.out_dtype, device=device))
@@ -978,6 +984,11 @@ class ForwardPlan:
         self._zero_init = []
         x = self.new(B, H, W, 8)
         mul, add, thr = (tuple(self.u8_io) + (0,))[:3] if self.u8_io else (1.0, 0.0, 0)      # (mul, add[, binarize_below])
+        if self.rng:
+            from .rng import STREAM_EPS, STREAM_NOISE
+            self._add(O.randn(self.eps, state=self.rng_state, stream_id=STREAM_EPS), "rng.eps", nbytes=self.eps.numel() * 4)
+            if self.noise is not None:
+                self._add(O.randn(self.noise, state=self.rng_state, stream_id=STREAM_NOISE), "rng.noise", nbytes=self.noise.numel() * 4)
         src = self.x_in
         if self.canny:
             self._add(O.canny_u8(self.x_in, self.canny_edges, self.canny_ws, n=B, h=H, w=W, c=3, out_c=3, thr_dev=self.canny_thr), "input.canny",
@@ -1008,6 +1019,8 @@ class ForwardPlan:
         self.free(z)
         self._add(O.nhwc_to_nchw(y.t, self.out, n=B, c=3, h=H, w=W, ldx=y.c, clamp=1, mul=0.5, add=0.5), "output.from_nhwc",
                   nbytes=B * H * W * (y.c * self.esz + 3 * self.out.element_size()))
+        if self.rng:          # last: every fill of one run saw the same step
+            self._add(O.randn(None, state=self.rng_state, kind=K.RANDN_ADVANCE), "rng.advance")
         for t in self._zero_init:
             t.zero_()
 
@@ -1036,6 +1049,14 @@ class ForwardPlan:
         lo, hi = canny_thresholds(low, high)
         self.canny_thr[0:1].fill_(lo)          # (fill kernels: the values travel as launch arguments, no host buffer to keep alive)
         self.canny_thr[1:2].fill_(hi)
+
+    def set_seed(self, seed, step=0):
+        """Write the noise state the next run / replay starts from: ``seed`` (reduced mod 2^64) and ``step``.  Every run advances the step
+        by one, so set_seed(s) followed by k replays draws steps 0 .. k-1.  Asynchronous on the current stream."""
+        assert self.rng, "this plan does not draw its own noise (get_plan(..., rng=True))"
+        from .rng import as_i32, pack_state
+        for i, word in enumerate(pack_state(seed, step)):
+            self.rng_state[i:i + 1].fill_(as_i32(word))          # (fill kernels, as set_canny_thresholds)
 
     def _prepare(self):
         if self.released:

@@ -12,7 +12,9 @@ torch storage an op pointer refers to, and a relocation table (op, pointer field
 recycling pool and its boundary buffers are *scratch* (size only, zero-filled at load); everything else -- packed weights with the LoRA
 merged at the current scale, norm parameters, device scalars, ticket counters -- is saved with its contents.  The boundary buffers get
 names: "x", "ctx", "eps", "noise" (stochastic plans), "out", and "canny_thr" (plans with the Canny op in front: two int32 {low, high},
-saved with the values of the export, which a host overwrites with i2i_plan_write to move the thresholds).
+saved with the values of the export, which a host overwrites with i2i_plan_write to move the thresholds), and "seed" (plans that draw
+their own noise, --seed N: the 16-byte state {seed_lo, seed_hi, step, reserved} of i2i_randn_params, saved with the exported seed at step 0;
+the program overwrites "eps" / "noise", which a host may read back, and advances the step after every run).
 
 This replaces the reference's ``model(...)`` call (src/pix2pix_turbo.py:186-219, src/cyclegan_turbo.py:241-254) for hosts that are not
 Python; the planner itself (route queries, tile choices, buffer recycling) stays in plan.py and runs once, at export.
@@ -58,10 +60,12 @@ def export_plan(plan, path, extra_tensors=()):
     # plan._finish_gn_scratch; produced inside the program, zero at rest)
     if getattr(plan, "canny", False):
         named["canny_thr"] = plan.canny_thr
+    if getattr(plan, "rng", False):
+        named["seed"] = plan.rng_state
     gn_scratch = [t for t in (getattr(plan, n, None) for n in ("gn_partial", "gn_ss", "gn_counters")) if t is not None]
     if getattr(plan, "canny", False):
         gn_scratch += [plan.canny_edges, plan.canny_ws]
-    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr",), holders=[plan] + list(extra_tensors), device=plan.device)
+    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed"), holders=[plan] + list(extra_tensors), device=plan.device)
 
 
 def export_text_plan(encoder, batch, path):
@@ -166,7 +170,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--direction a2b] [--u8 [--canny LOW HIGH]] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--direction a2b] [--u8 [--canny LOW HIGH]] [--seed N] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -184,6 +188,9 @@ def main(argv=None):
     ap.add_argument("--canny", type=float, nargs=2, default=None, metavar=("LOW", "HIGH"), help="with --u8 (pix2pix): 'x' holds photos; the program "
                     "starts with Canny edge detection (canny_from_pil, src/inference_paired.py:47-50).  LOW HIGH are the thresholds saved in the file; "
                     "a host moves them by writing two int32 to the buffer named 'canny_thr'")
+    ap.add_argument("--seed", type=int, default=None, help="the program draws 'eps' (and 'noise') itself: seeded noise under the contract of "
+                    "i2i_randn_params (include/i2i_turbo.h).  N is the seed saved in the file (step 0); a host sets another by writing four "
+                    "uint32 {seed_lo, seed_hi, step, 0} to the buffer named 'seed'")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--base-dir", default=None, help="local stabilityai/sd-turbo snapshot directory")
     ap.add_argument("--pretrained-path", default=None, help="the reference's LoRA checkpoint (.pkl)")
@@ -211,7 +218,7 @@ def main(argv=None):
         from .cyclegan_turbo import CycleGAN_Turbo
         model = CycleGAN_Turbo(**kw)
         u8 = (2.0, -1.0) if a.u8 else None          # CycleGAN callers normalise to [-1, 1] (src/inference_unpaired.py:42-44)
-        plan = model.get_plan(a.batch, H, W, direction=a.direction, u8_io=u8)
+        plan = model.get_plan(a.batch, H, W, direction=a.direction, u8_io=u8, rng=a.seed is not None)
     else:
         from .pix2pix_turbo import Pix2Pix_Turbo
         model = Pix2Pix_Turbo(**kw)
@@ -219,9 +226,11 @@ def main(argv=None):
         # `F.to_tensor(img) < 0.5`), which is what Pix2Pix_Turbo.forward_u8(..., sketch=True) feeds -- a stochastic plan is the sketch model
         u8 = ((1.0, 0.0, 128) if (a.sketch or a.stochastic) else (1.0, 0.0)) if a.u8 else None
         gamma = a.gamma if a.gamma is not None else (0.4 if a.stochastic else 1.0)
-        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=a.canny is not None)
+        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=a.canny is not None, rng=a.seed is not None)
         if a.canny is not None:
             plan.set_canny_thresholds(*a.canny)
+    if a.seed is not None:
+        plan.set_seed(a.seed, 0)
     info = export_plan(plan, a.out)                 # (re-merges the weights at this plan's r first: plan._prepare)
     print("wrote %s: %d ops, %d buffers, %.2f GB of weights, %.2f GB of scratch at load; boundary buffers %s"
           % (a.out, info["ops"], info["buffers"], info["data_bytes"] / 1e9, info["scratch_bytes"] / 1e9, info["io"]))

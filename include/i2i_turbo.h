@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define I2I_ABI_VERSION 11
+#define I2I_ABI_VERSION 12
 
 typedef enum { I2I_F32 = 0, I2I_BF16 = 1, I2I_F16 = 2,
                I2I_U8 = 3   /* only as src_dtype / dst_dtype of the boundary layout ops: uint8 images, HWC interleaved */
@@ -53,7 +53,8 @@ typedef enum {
     I2I_OP_LORA_MERGE = 12,
     I2I_OP_RESIZE_U8 = 13,
     I2I_OP_NOP = 14,           /* one empty kernel launch (bench.py's calibration: microseconds per hipGraph node) */
-    I2I_OP_CANNY_U8 = 15
+    I2I_OP_CANNY_U8 = 15,
+    I2I_OP_RANDN = 16
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -301,6 +302,43 @@ typedef struct {
     void* ws;                          /* >= i2i_canny_ws_bytes(n, h, w) bytes, 16-byte aligned; contents irrelevant before and after */
 } i2i_canny_u8_params;
 
+/* Seeded Gaussian noise on the device (ABI v12): the `torch.manual_seed(seed); torch.randn(...)` of the reference's inference scripts
+ * (src/inference_paired.py:58-60, the seed slider of gradio_sketch2image.py:80-82) as an op of the program, so that one plan, one
+ * captured graph and one plan file serve every seed and a replay draws fresh noise without the host.  Bit parity with torch.randn or
+ * cuRAND is NOT a goal (neither stream is specified, and torch-ROCm's differs from CUDA's); this is the contract, and
+ * tests/randn_ref.py is its CPU oracle (integer Philox + an fp64 transform).
+ *
+ * Counter based and stateless per element: the bits do not depend on the grid.
+ *   STATE    four uint32 {seed_lo, seed_hi, step, reserved}; the reserved word is ignored, whatever it holds.
+ *   ELEMENT  i (0-based flat index into dst), q = i >> 2: lane i & 3 of Philox4x32-10 with counter
+ *            {q & 0xffffffff, q >> 32, step, stream_id} and key {seed_lo, seed_hi}.  Random123 constants: multipliers 0xD2511F53 /
+ *            0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85, 10 rounds, the key bumped after each round.  One round maps
+ *            (c0, c1, c2, c3) to (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)).  A tail with n % 4 != 0
+ *            drops the unused lanes.
+ *   RAW      dst is uint32: the words as they are.
+ *   NORMAL   dst is fp32: the words (w0, w1) and (w2, w3) are two Box-Muller pairs (wa, wb):
+ *              u1 = ((wa >> 8) + 1) * 2^-24   in (0, 1], exact in fp32;   u2 = (wb >> 8) * 2^-24   in [0, 1)
+ *              rad = sqrtf(-2 * logf(u1));   outputs rad * cospif(2 * u2), rad * sinpif(2 * u2)
+ *            with the precise library functions (logf and the pi-scaled trigonometric functions at <= 1 ulp, sqrtf correctly
+ *            rounded) -- no fast forms, no fp32 product 2*pi*u2.  Each output is within rad * 2^-21 of the exact transform of
+ *            the same words (logf's ulp halved by the root, the root, 4 * 2^-24 absolute for the trigonometric value, the product),
+ *            exactly 0 where rad = 0, and |x| <= sqrt(48 ln 2) ~ 5.77.
+ *   ADVANCE  one thread does state[2] += 1 (wrapping); nothing else is written.  Stream order serialises it.
+ * Stream ids of a planned forward: 0 = "eps" (the posterior draw), 2 = "noise" (the sketch model's noise_map); 1 is reserved for the
+ * reference's numerically dead scheduler draw and never generated.  The index is flat, so image 0 of a batch gets the noise a
+ * batch-1 run gets at the same (seed, step).
+ * dst needs 4-byte alignment only (slices are fine); nothing is written outside dst[0 .. n-1].  With `state` set the device state is
+ * read at run time (like canny_u8.thr_dev); with state = NULL the immediate seed / step are used. */
+typedef enum { I2I_RANDN_NORMAL = 0, I2I_RANDN_RAW = 1, I2I_RANDN_ADVANCE = 2 } i2i_randn_kind;
+typedef struct {
+    void* dst;                         /* fp32 (normal) or uint32 (raw) [n]; ignored by advance */
+    int64_t n;
+    const uint32_t* state;             /* optional device {seed_lo, seed_hi, step, reserved}; advance writes state[2] */
+    uint64_t seed; uint32_t step;      /* used when state == NULL */
+    uint32_t stream_id;
+    int32_t kind;                      /* i2i_randn_kind */
+} i2i_randn_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -322,6 +360,7 @@ typedef struct {
         i2i_resize_u8_params resize_u8;
         i2i_nop_params nop;
         i2i_canny_u8_params canny_u8;
+        i2i_randn_params randn;
     } u;
 } i2i_op;
 
@@ -354,6 +393,7 @@ int i2i_lora_merge(const i2i_lora_merge_params* p, int dtype, void* stream);
 int i2i_resize_u8(const i2i_resize_u8_params* p, int dtype, void* stream);   /* dtype ignored (uint8 data) */
 int i2i_canny_u8(const i2i_canny_u8_params* p, int dtype, void* stream);     /* dtype ignored (uint8 data); five launches */
 size_t i2i_canny_ws_bytes(int n, int h, int w);                              /* bytes of i2i_canny_u8_params.ws (0 for a non-positive size) */
+int i2i_randn(const i2i_randn_params* p, int dtype, void* stream);           /* dtype ignored (fp32 / uint32 data); one launch */
 
 /* ---- calibration micro-kernels (csrc/calib.hip; bench.py's `calib` block: what THIS box delivers on three elementary loads, so that
  * lines measured on different boxes of a pool can be compared).  Not on the forward path. */
@@ -378,7 +418,8 @@ int i2i_graph_destroy(void* graph);
  * relocation table), loaded and run without Python.  The whole-forward entry for C / C++ hosts: what `model(x, caption_enc=..., eps=...)`
  * (src/pix2pix_turbo.py:186-219) is for a Python host, for one fixed (batch, size, dtype, mode).  Names of the pix2pix / CycleGAN plans:
  * "x" (fp32 NCHW images in [-1, 1], or uint8 NHWC with the u8 boundary), "ctx" ([1 | B][77][1024] text states in the plan's dtype),
- * "eps" (fp32 [B][4][H/8][W/8] posterior noise), "noise" (stochastic plans), "out" (images, NCHW in the plan's output dtype or uint8 NHWC).
+ * "eps" (fp32 [B][4][H/8][W/8] posterior noise), "noise" (stochastic plans), "out" (images, NCHW in the plan's output dtype or uint8 NHWC);
+ * plans exported with a seed also have "seed" (16 bytes: the i2i_randn_params state; the program then fills "eps" / "noise" itself).
  * load / write / read are synchronous; run only enqueues (i2i_run); i2i_plan_ops() hands the program to i2i_graph_create(). */
 int i2i_plan_load(const char* path, void** plan_out);
 int i2i_plan_io(void* plan, const char* name, void** dev_ptr, size_t* bytes);       /* device address + size of a named buffer */
