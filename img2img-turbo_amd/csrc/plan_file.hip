@@ -11,10 +11,13 @@
 //
 // File layout (little endian, 8-byte aligned sections):
 //   header   : "I2IPLAN1", u32 abi, u32 sizeof(i2i_op), u32 n_ops, u32 n_bufs, u32 n_relocs, u32 n_io
+//              "I2IPLAN2" (exported with live_scale) adds: u32 n_scale_ops, u32 pad -- the op table then holds n_ops forward ops followed by
+//              n_scale_ops ops of the scale program (I2I_OP_LORA_MERGE per adapted layer, I2I_OP_TWIN_FOLD), relocations index the
+//              concatenated array, and the buffers the scale ops point at (fp32 masters, A, B, the (r, gamma) pairs) are saved with contents
 //   bufs     : n_bufs  x { u64 bytes; u32 kind (0 = scratch, zero-filled; 1 = contents follow in the data section); u32 pad }
 //   io       : n_io    x { char name[24]; u32 buf; u32 pad; u64 offset; u64 bytes }
 //   relocs   : n_relocs x { u32 op; u32 field_offset (bytes inside i2i_op); u32 buf; u32 pad; u64 offset }   -> *(void**)(op + field_offset) = base[buf] + offset
-//   ops      : n_ops x sizeof(i2i_op) bytes (pointer fields are meaningless until patched; non-pointer fields verbatim)
+//   ops      : (n_ops + n_scale_ops) x sizeof(i2i_op) bytes (pointer fields are meaningless until patched; non-pointer fields verbatim)
 //   data     : the contents of every kind-1 buffer, in buffer order
 //
 // What the loader checks (a plan file is an EXECUTABLE artefact -- it names kernels, shapes and strides -- so it deserves the trust of the
@@ -41,6 +44,7 @@ int rt_upload(void* dst, const void* src, size_t bytes);
 int rt_download(void* dst, const void* src, size_t bytes);
 int rt_zero(void* dst, size_t bytes);
 int rt_sync();
+int set_rg(float* rg, float r, float gamma, void* stream);      // lora_merge.hip: one small launch
 }  // namespace i2i
 
 namespace {
@@ -53,8 +57,16 @@ struct Plan {
     std::vector<void*> base;
     std::vector<BufRec> bufs;
     std::vector<IoRec> io;
-    std::vector<i2i_op> ops;
-    ~Plan() { for (void* p : base) if (p) i2i::rt_free(p); }
+    std::vector<i2i_op> ops;                  // the forward, then (v2 files) the scale program as exported
+    size_t n_fwd = 0;
+    bool has_scale = false;
+    std::vector<void*> groups;                // the plain merges of the scale program, one i2i_merge_group per dtype
+    std::vector<i2i_op> scale_rest;           // what runs per op after the groups: LayerNorm-fold merges, the TwinConv fold
+    std::vector<float*> rgs;                  // every distinct device (r, gamma) pair the plan reads
+    ~Plan() {
+        for (void* g : groups) i2i_merge_group_destroy(g);
+        for (void* p : base) if (p) i2i::rt_free(p);
+    }
 };
 
 bool read_exact(FILE* f, void* dst, size_t n) { return n == 0 || fread(dst, 1, n, f) == n; }
@@ -81,6 +93,9 @@ const std::vector<size_t>& ptr_fields(int opcode) {
     static const std::vector<size_t> resize = {PF(resize_u8, src), PF(resize_u8, dst), PF(resize_u8, bounds), PF(resize_u8, coeffs)};
     static const std::vector<size_t> canny = {PF(canny_u8, src), PF(canny_u8, dst), PF(canny_u8, thr_dev), PF(canny_u8, ws)};
     static const std::vector<size_t> randn = {PF(randn, dst), PF(randn, state)};
+    static const std::vector<size_t> twin = {PF(twin_fold, dst), PF(twin_fold, bias), PF(twin_fold, w_pre), PF(twin_fold, a_pre), PF(twin_fold, b_pre),
+                                             PF(twin_fold, bias_pre), PF(twin_fold, w_cur), PF(twin_fold, a_cur), PF(twin_fold, b_cur), PF(twin_fold, bias_cur),
+                                             PF(twin_fold, rg)};
     switch (opcode) {
         case I2I_OP_IGEMM: return igemm;
         case I2I_OP_GN_STATS: return gn_stats;
@@ -97,6 +112,7 @@ const std::vector<size_t>& ptr_fields(int opcode) {
         case I2I_OP_RESIZE_U8: return resize;
         case I2I_OP_CANNY_U8: return canny;
         case I2I_OP_RANDN: return randn;
+        case I2I_OP_TWIN_FOLD: return twin;
         default: return none;
     }
 }
@@ -128,10 +144,18 @@ static int plan_load_impl(const char* path, void** plan_out) {
     std::unique_ptr<Plan> pl(new Plan());
     auto bail = [&](int code, const char* what) { return i2i::fail(code, "plan_load(%s): %s", path, what); };
     Header h;
-    if (!read_exact(f, &h, sizeof(h)) || memcmp(h.magic, "I2IPLAN1", 8) != 0) return bail(I2I_ERR_BAD_ARG, "not a plan file");
+    if (!read_exact(f, &h, sizeof(h))) return bail(I2I_ERR_BAD_ARG, "not a plan file");
+    const bool v2 = memcmp(h.magic, "I2IPLAN2", 8) == 0;
+    if (!v2 && memcmp(h.magic, "I2IPLAN1", 8) != 0) return bail(I2I_ERR_BAD_ARG, "not a plan file");
+    uint32_t ext[2] = {0, 0};                 // v2: {n_scale_ops, pad}
+    if (v2 && !read_exact(f, ext, sizeof(ext))) return bail(I2I_ERR_BAD_ARG, "not a plan file");
     if (h.abi != (uint32_t)I2I_ABI_VERSION || h.sizeof_op != (uint32_t)sizeof(i2i_op))
         return bail(I2I_ERR_BAD_ARG, "written for another ABI version / i2i_op layout: export it again with this library");
-    if (h.n_ops > (1u << 20) || h.n_bufs > (1u << 20) || h.n_relocs > (1u << 24) || h.n_io > 64) return bail(I2I_ERR_BAD_ARG, "implausible header");
+    if (h.n_ops > (1u << 20) || h.n_bufs > (1u << 20) || h.n_relocs > (1u << 24) || h.n_io > 64 || ext[0] > (1u << 20)) return bail(I2I_ERR_BAD_ARG, "implausible header");
+    const uint32_t n_fwd = h.n_ops;
+    h.n_ops += ext[0];                        // every check below runs over the concatenated op array
+    pl->n_fwd = n_fwd;
+    pl->has_scale = v2;
     pl->bufs.resize(h.n_bufs);
     pl->io.resize(h.n_io);
     std::vector<RelocRec> rel(h.n_relocs);
@@ -148,6 +172,8 @@ static int plan_load_impl(const char* path, void** plan_out) {
     for (uint32_t i = 0; i < h.n_ops; ++i) {
         const std::vector<size_t>& pf = ptr_fields(pl->ops[i].opcode);
         if (pf.empty() && pl->ops[i].opcode != I2I_OP_NOP) return bail(I2I_ERR_BAD_ARG, "unknown opcode in the program");
+        if (i >= n_fwd && pl->ops[i].opcode != I2I_OP_LORA_MERGE && pl->ops[i].opcode != I2I_OP_TWIN_FOLD)
+            return bail(I2I_ERR_BAD_ARG, "the scale program holds an op that is neither a merge nor a TwinConv fold");
         for (size_t off : pf) {
             void* v;
             memcpy(&v, (const char*)&pl->ops[i] + off, sizeof(void*));
@@ -187,6 +213,43 @@ static int plan_load_impl(const char* path, void** plan_out) {
         void* v = (char*)pl->base[r.buf] + r.offset;
         memcpy((char*)&pl->ops[r.op] + r.field_offset, &v, sizeof(void*));
     }
+    if (v2) {
+        // the scale program: plain merges go into one group per dtype (i2i_merge_group_create checks each layer again), the rest stays per op
+        auto add_rg = [&](const float* rg) {
+            if (!rg) return;
+            for (float* q : pl->rgs) if (q == rg) return;
+            pl->rgs.push_back((float*)rg);
+        };
+        for (int dt = I2I_F32; dt <= I2I_F16; ++dt) {
+            std::vector<i2i_lora_merge_params> layers;
+            for (size_t i = n_fwd; i < pl->ops.size(); ++i) {
+                const i2i_op& op = pl->ops[i];
+                const i2i_lora_merge_params& m = op.u.lora_merge;
+                if (op.opcode == I2I_OP_LORA_MERGE && op.dtype == dt && !(m.kscale || m.kshift || m.colsum || m.bias_out)) layers.push_back(m);
+            }
+            if (layers.empty()) continue;
+            void* g = nullptr;
+            if (i2i_merge_group_create(layers.data(), (int)layers.size(), dt, &g) != I2I_OK) {
+                char tmp[400];
+                snprintf(tmp, sizeof(tmp), "scale program: %s", i2i::error_buffer());
+                return bail(I2I_ERR_BAD_ARG, tmp);
+            }
+            pl->groups.push_back(g);
+        }
+        for (size_t i = n_fwd; i < pl->ops.size(); ++i) {
+            const i2i_op& op = pl->ops[i];
+            if (op.opcode == I2I_OP_TWIN_FOLD) {
+                add_rg(op.u.twin_fold.rg);
+                pl->scale_rest.push_back(op);
+            } else {
+                const i2i_lora_merge_params& m = op.u.lora_merge;
+                add_rg(m.rg);
+                if (op.dtype < I2I_F32 || op.dtype > I2I_F16 || m.kscale || m.kshift || m.colsum || m.bias_out) pl->scale_rest.push_back(op);
+            }
+        }
+        for (size_t i = 0; i < n_fwd; ++i)
+            if (pl->ops[i].opcode == I2I_OP_POSTERIOR) add_rg(pl->ops[i].u.posterior.r_dev);
+    }
     // the zero-fills above are asynchronous with respect to a NON-BLOCKING stream the caller may run the plan on right away
     if (i2i::rt_sync() != I2I_OK) return bail(I2I_ERR_RUNTIME, "device synchronisation failed");
     *plan_out = pl.release();
@@ -225,14 +288,32 @@ extern "C" int i2i_plan_ops(void* plan, const i2i_op** ops, int* n_ops) {
     if (!plan || !ops || !n_ops) return i2i::fail(I2I_ERR_BAD_ARG, "plan_ops: null argument");
     const Plan* pl = (const Plan*)plan;
     *ops = pl->ops.data();
-    *n_ops = (int)pl->ops.size();
+    *n_ops = (int)pl->n_fwd;
     return I2I_OK;
 }
 
 extern "C" int i2i_plan_run(void* plan, void* stream) {
     if (!plan) return i2i::fail(I2I_ERR_BAD_ARG, "plan_run: null plan");
     const Plan* pl = (const Plan*)plan;
-    return i2i_run(pl->ops.data(), (int)pl->ops.size(), stream);
+    return i2i_run(pl->ops.data(), (int)pl->n_fwd, stream);
+}
+
+extern "C" int i2i_plan_has_scale(void* plan) { return plan && ((const Plan*)plan)->has_scale ? 1 : 0; }
+
+extern "C" int i2i_plan_set_scale(void* plan, float r, float gamma, void* stream) {
+    if (!plan) return i2i::fail(I2I_ERR_BAD_ARG, "plan_set_scale: null plan");
+    const Plan* pl = (const Plan*)plan;
+    if (!pl->has_scale)
+        return i2i::fail(I2I_ERR_UNSUPPORTED, "plan_set_scale: this plan file carries no scale program (its weights are merged at the export scale): export it with live_scale");
+    for (float* rg : pl->rgs) {
+        const int rc = i2i::set_rg(rg, r, gamma, stream);
+        if (rc != I2I_OK) return rc;
+    }
+    for (void* g : pl->groups) {
+        const int rc = i2i_merge_group_run(g, stream);
+        if (rc != I2I_OK) return rc;
+    }
+    return i2i_run(pl->scale_rest.data(), (int)pl->scale_rest.size(), stream);
 }
 
 extern "C" int i2i_plan_destroy(void* plan) {

@@ -166,6 +166,19 @@ def randn(dst, *, n=None, state=None, seed=0, step=0, stream_id=0, kind=K.RANDN_
     return K.OP_RANDN, _keep(p, dst, state)
 
 
+def twin_fold(dst, bias, pre, cur, rg, *, bias_pre=None, bias_cur=None):
+    """dst[N][K] (+ bias[N]) = the TwinConv fold of two packed layers at the device scale rg[0] (i2i_twin_fold_params).  ``pre`` / ``cur``:
+    (w0 fp32 [N][K], A fp32 [rank][K] or None, B fp32 [N][rank] or None)."""
+    p = K.TwinFoldParams()
+    (w0, a0, b0), (w1, a1, b1) = pre, cur
+    p.dst, p.bias, p.rg = ptr(dst), ptr(bias), ptr(rg)
+    p.w_pre, p.a_pre, p.b_pre, p.bias_pre = ptr(w0), ptr(a0), ptr(b0), ptr(bias_pre)
+    p.w_cur, p.a_cur, p.b_cur, p.bias_cur = ptr(w1), ptr(a1), ptr(b1), ptr(bias_cur)
+    p.N, p.K = w0.shape
+    p.rank_pre, p.rank_cur = (0 if a0 is None else a0.shape[0]), (0 if a1 is None else a1.shape[0])
+    return K.OP_TWIN_FOLD, _keep(p, dst, bias, w0, a0, b0, bias_pre, w1, a1, b1, bias_cur, rg)
+
+
 def nhwc_to_nchw(x, y, *, n, c, h, w, ldx, clamp=0, mul=0.0, add=0.0):
     """y: NCHW float tensor, or a uint8 HWC image batch [n, h, w, c] (then y = trunc(clamp01(x*mul+add)*255))."""
     p = K.NhwcToNchwParams()

@@ -9,7 +9,8 @@ hipGraphs stay valid).
                       as side branches: src/pix2pix_turbo.py:69,74,206-207).  Per adapted layer the device keeps the fp32
                       master W in packed layout, A (scaling folded in, adapters concatenated along rank) and B.
   * skip gamma        skip_conv_i(skip * gamma) = (gamma * W') skip: folded into the skip-conv weights by the same kernel
-  * TwinConv fold     W = pre*(1-r) + cur*r (tiny; re-folded on the host per r)     (src/pix2pix_turbo.py:16-26)
+  * TwinConv fold     W = pre*(1-r) + cur*r (tiny; re-folded on the host per r, or -- live_scale -- by the device kernel
+                      i2i_twin_fold)                                          (src/pix2pix_turbo.py:16-26)
   * time-embedding    t = 999 is fixed (src/pix2pix_turbo.py:160) so time_emb_proj(silu(temb)) is a
                       per-resnet constant added to conv1's bias
   * conv_out o quant_conv of the VAE encoder composed into one 3x3 conv (both linear, nothing between)
@@ -46,9 +47,52 @@ def subpixel_weights(w):
     return out.reshape(4, o, 2, 2, i)
 
 
-class Packer:
-    def __init__(self, sd: Dict[str, torch.Tensor], scaling: Dict[str, float], dtype, device, lib, r: float = 1.0, gamma: float = 1.0):
+class ScaleProgram:
+    """Everything a new (r, gamma) has to run for one packer once the device pair ``rg`` holds it: the merge group (every plain adapted
+    layer in one launch), the layers left per-layer (the LayerNorm-fold form: one workgroup per row block for its row sums -- or all of
+    them with ``grouped=False``) and the TwinConv fold.  ``all_ops`` is the same work as a flat per-layer program: what a plan file stores
+    (the loader builds its own group from it)."""
+
+    def __init__(self, lib, dt, merges, twin, grouped=True):
         from . import _capi
+        self.lib, self.groups = lib, []
+        plain = [p for p in merges if not p.kscale] if grouped else []
+        rest = [p for p in merges if p.kscale] if grouped else list(merges)
+        if plain:
+            self.groups.append(lib.merge_group_create(plain, dt))
+        self.n_grouped, self.n_layers = len(plain), len(merges)
+        self.prog, self.all_ops = _capi.Program(), _capi.Program()
+        for prog, layers in ((self.prog, rest), (self.all_ops, merges)):
+            for i, p in enumerate(layers):
+                prog.add(_capi.OP_LORA_MERGE, dt, p, "scale.merge%d" % i)
+            if twin is not None:
+                prog.add(_capi.OP_TWIN_FOLD, dt, twin, "scale.twin_fold")
+            prog.freeze()
+
+    def run(self, stream=0):
+        """Enqueue on ``stream`` (a raw hipStream_t value); asynchronous."""
+        for g in self.groups:
+            self.lib.merge_group_run(g, stream)
+        if self.prog.n:
+            self.lib.run(self.prog, stream)
+
+    def __del__(self):
+        groups, self.groups = self.groups, []
+        for g in groups:
+            try:
+                self.lib.merge_group_destroy(g)
+            except Exception:      # (interpreter shutdown: the binding may already be gone)
+                pass
+
+
+class Packer:
+    GROUPED = True           # scale_program(): plain layers in one grouped launch (False: every layer stays a per-layer op)
+
+    def __init__(self, sd: Dict[str, torch.Tensor], scaling: Dict[str, float], dtype, device, lib, r: float = 1.0, gamma: float = 1.0, live_scale: bool = False):
+        from . import _capi
+        self.live_scale = bool(live_scale)   # set_scale runs the scale program (device TwinConv fold, grouped merge) instead of the per-layer loop + host refold
+        self._twin = None                    # TwinFoldParams of conv_in (live_scale packers of a TwinConv checkpoint)
+        self._scale_prog = None
         self.sd = sd
         self.scaling = dict(scaling)          # adapter -> lora_alpha / rank (the per-call factor r is applied on the device)
         self.dtype = dtype
@@ -140,7 +184,9 @@ class Packer:
             assert Ad.shape == (A.shape[0], k) and Bd.shape == (n, A.shape[0]), (Ad.shape, Bd.shape, n, k)
             p.a, p.b, p.rank = Ad.data_ptr(), Bd.data_ptr(), A.shape[0]
             keep += [Ad, Bd]
+        p._keep = tuple(t for t in keep if t is not None)      # (plan_file.export_program finds the storages through it)
         self._merges.append((p, keep))
+        self._scale_prog = None
         self.lib.check(self.lib.lib.i2i_lora_merge(C_addr(p), self._dt, self._stream()))
         return dst
 
@@ -158,12 +204,24 @@ class Packer:
         if float(r) == self.r and float(gamma) == self.gamma:
             return
         self.r, self.gamma = float(r), float(gamma)
+        if self.live_scale:      # two fills and the scale program, all on the current stream: no host tensor, no upload
+            self.rg[0:1].fill_(self.r)
+            self.rg[1:2].fill_(self.gamma)
+            st = self._stream()
+            self.scale_program().run(st.value or 0 if st is not None else 0)
+            return
         self.rg.copy_(torch.tensor([self.r, self.gamma], dtype=torch.float32))
         st = self._stream()
         for p, _ in self._merges:
             self.lib.check(self.lib.lib.i2i_lora_merge(C_addr(p), self._dt, st))
         for f in self._refolds:
             f()
+
+    def scale_program(self) -> ScaleProgram:
+        """The scale program of everything packed so far (rebuilt after another layer was packed): see ScaleProgram."""
+        if self._scale_prog is None:
+            self._scale_prog = ScaleProgram(self.lib, self._dt, [p for p, _ in self._merges], self._twin, grouped=self.GROUPED)
+        return self._scale_prog
 
     @staticmethod
     def _conv_to_k(w, split=None):
@@ -242,6 +300,27 @@ class Packer:
     def twin_conv_in(self):
         """UNet conv_in as TwinConv folded at the current r (src/pix2pix_turbo.py:23-26); re-folded by set_scale."""
         key = ("conv", "conv_in", None)
+        if key not in self.cache and self.live_scale:
+            # the fold is a kernel (i2i_twin_fold): both branches stay on the device as packed fp32 masters + LoRA factors, part of scale_program()
+            from . import ops as O
+
+            def packed(name):
+                w, b = self.base(name)
+                ab = self.lora(name)
+                A = B = None
+                if ab is not None:
+                    A, B = self._up(self._conv_to_k(ab[0]), torch.float32), self._up(ab[1], torch.float32)
+                return (self._up(self._conv_to_k(w), torch.float32), A, B), self._up(b, torch.float32)
+            pre, bpre = packed("conv_in.conv_in_pretrained")
+            cur, bcur = packed("conv_in.conv_in_curr")
+            n, k = pre[0].shape
+            dst = torch.empty(n, k, dtype=self.dtype, device=self.device)
+            bias = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.nbytes += dst.numel() * dst.element_size() + 4 * n
+            _, p = O.twin_fold(dst, bias, pre, cur, self.rg, bias_pre=bpre, bias_cur=bcur)
+            self._twin, self._scale_prog = p, None
+            self.lib.check(self.lib.lib.i2i_twin_fold(C_addr(p), self._dt, self._stream()))
+            self.cache[key] = dict(w=dst, b=bias, n=n, ks=3)
         if key not in self.cache:
             def fold():
                 w1, b1 = self.merged("conv_in.conv_in_pretrained")

@@ -65,11 +65,16 @@ class TurboGeneratorBase(torch.nn.Module):
     MAX_PLANS = 8          # distinct (batch, size, mode) programs kept alive; each owns an activation pool + a hipGraph
 
     def __init__(self, weights: GeneratorWeights, device="cuda", dtype=torch.float32, lib=None,
-                 tokenizer=None, text_encoder=None, use_graph=True, fuse_gn=True, flash=True, plan_options=None, unet_dtype=None):
+                 tokenizer=None, text_encoder=None, use_graph=True, fuse_gn=True, flash=True, plan_options=None, unet_dtype=None, live_scale=False):
         """``dtype``: element type of activations and packed weights (fp32 = the exact-MFMA parity mode).  ``unet_dtype``: another 16-bit
         type for the UNet alone -- ``dtype=torch.bfloat16, unet_dtype=torch.float16`` keeps the VAE (whose real activations overflow fp16)
-        in bf16 and gives the UNet, whose error the 1-step scheduler multiplies by 14.6, fp16's three extra mantissa bits."""
+        in bf16 and gives the UNet, whose error the 1-step scheduler multiplies by 14.6, fp16's three extra mantissa bits.
+        ``live_scale=True``: ``set_lora_scale(r)`` writes the device pair (r, gamma) and runs each packer's scale program
+        (Packer.scale_program: one grouped merge launch, the LayerNorm-fold layers, the TwinConv fold as a kernel) -- asynchronous on the
+        stream with no host tensor math.  Off (the default), the per-layer loop and the host TwinConv fold run as before; the device fold
+        rounds differently from torch's host fold, so a TwinConv checkpoint's outputs differ in the last bits between the two settings."""
         super().__init__()
+        self.live_scale = bool(live_scale)
         self.unet_dtype_ = unet_dtype
         self.weights = weights
         self.device_ = torch.device(device)
@@ -133,7 +138,7 @@ class TurboGeneratorBase(torch.nn.Module):
             w = self.weights
             sd, sc = {"unet": (w.unet, w.unet_scaling), "vae": (w.vae, w.vae_scaling), "vae_b2a": (w.vae_b2a, w.vae_scaling)}[which]
             with self._on_device():
-                self._packers[key] = Packer(sd, sc, dt, self.device_, self.lib, self._r, self._r)
+                self._packers[key] = Packer(sd, sc, dt, self.device_, self.lib, self._r, self._r, live_scale=self.live_scale)
         return self._packers[key]
 
     def _get_packers(self, direction):

@@ -28,6 +28,7 @@ import torch
 from . import _capi as K
 
 MAGIC = b"I2IPLAN1"
+MAGIC_LIVE = b"I2IPLAN2"      # exported with live_scale: the header also counts the scale program's ops, stored after the forward's
 
 
 def _pointer_fields():
@@ -45,9 +46,28 @@ def _storage_key(t):
     return s.data_ptr(), s.nbytes()
 
 
-def export_plan(plan, path, extra_tensors=()):
+def scale_program_of(plan):
+    """The scale programs of the plan's packers as ONE flat per-layer program (Packer.scale_program().all_ops of the UNet's, then the VAE's):
+    what a live_scale plan file stores after the forward."""
+    prog = K.Program()
+    for which, pk in (("unet", plan.pu), ("vae", plan.pv)):
+        if pk._refolds:
+            raise K.I2IError("export_plan(live_scale=True): the %s packer folds its TwinConv on the host -- construct the model with "
+                             "live_scale=True, so that the fold is an op a C host can run" % which)
+        sp = pk.scale_program()
+        for opcode, dtype, params, label in sp.all_ops.ops:
+            prog.add(opcode, dtype, params, "%s.%s" % (which, label))
+        prog.keep.append(sp)
+    return prog.freeze()
+
+
+def export_plan(plan, path, extra_tensors=(), live_scale=False):
     """Write ``plan`` (a ForwardPlan) to ``path``.  Returns a small summary dict.  The plan must not be replaying while this runs
     (the buffers' contents are read back through torch).
+
+    ``live_scale=True``: the file (magic "I2IPLAN2") also carries the scale program -- every per-layer merge op and the TwinConv fold, with
+    the fp32 masters, A, B and the device (r, gamma) pairs they read -- so that a C host moves the LoRA scale with i2i_plan_set_scale().
+    Without it the file is an "I2IPLAN1" one whose weights stay merged at the export scale.
 
     The packed weights are SHARED by every plan of a model and hold whatever LoRA / skip scale ``r`` was merged last (another plan's
     ``r``, or 1.0 after a deterministic plan ran): ``plan._prepare()`` re-merges them at THIS plan's ``r`` before anything is read
@@ -65,7 +85,8 @@ def export_plan(plan, path, extra_tensors=()):
     gn_scratch = [t for t in (getattr(plan, n, None) for n in ("gn_partial", "gn_ss", "gn_counters")) if t is not None]
     if getattr(plan, "canny", False):
         gn_scratch += [plan.canny_edges, plan.canny_ws]
-    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed"), holders=[plan] + list(extra_tensors), device=plan.device)
+    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed"), holders=[plan] + list(extra_tensors), device=plan.device,
+                          scale_prog=scale_program_of(plan) if live_scale else None)
 
 
 def export_text_plan(encoder, batch, path):
@@ -79,11 +100,14 @@ def export_text_plan(encoder, batch, path):
     return export_program(tp.prog, path, {"ids": tp.ids, "ctx": tp.out}, scratch=list(tp._keep), holders=[tp, encoder.w], device=encoder.device)
 
 
-def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep_contents=()):
+def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep_contents=(), scale_prog=None):
     """The file writer behind both: ``prog`` (a frozen _capi.Program), ``named`` boundary tensors, ``scratch`` tensors whose contents need
     not be saved (zero-filled at load, like the boundary buffers), ``holders``: objects / tensors that own anything else the ops point at,
-    ``keep_contents``: names of boundary tensors that are saved WITH their contents (parameters with a meaningful default)."""
+    ``keep_contents``: names of boundary tensors that are saved WITH their contents (parameters with a meaningful default).
+    ``scale_prog``: a second frozen program stored after ``prog`` (the live_scale form, see export_plan)."""
     assert prog.array is not None, "the program is not frozen"
+    progs = [prog] + ([scale_prog] if scale_prog is not None else [])
+    all_ops = [(pg, i) for pg in progs for i in range(pg.n)]      # the concatenated op array relocations index
     named = dict(named)
     scratch_keys = {_storage_key(t) for t in list(scratch) + [t for n, t in named.items() if n not in keep_contents]}
     tensors = list(named.values()) + list(scratch)
@@ -102,7 +126,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
                 harvest(t, depth - 1)
     for hld in holders:
         harvest(hld, 2)
-    for _, _, params, _ in prog.ops:
+    for _, _, params, _ in [o for pg in progs for o in pg.ops]:
         tensors += [t for t in getattr(params, "_keep", ()) if isinstance(t, torch.Tensor)]
     storages = {}                                # (ptr, nbytes) -> a tensor that owns it
     for t in tensors:
@@ -119,14 +143,14 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
     # ---- relocations
     fields = _pointer_fields()
     relocs, used = [], set()
-    for oi in range(prog.n):
-        op = prog.array[oi]
+    for oi, (pg, li) in enumerate(all_ops):
+        op = pg.array[li]
         base = C.addressof(op)
         for off, fname in fields[op.opcode]:
             v = C.c_void_p.from_address(base + off).value
             if not v:
                 continue
-            b, o = locate(v, "op %d (%s) field %s" % (oi, prog.labels[oi], fname))
+            b, o = locate(v, "op %d (%s) field %s" % (oi, pg.labels[li], fname))
             relocs.append((oi, off, b, o))
             used.add(b)
     io = []
@@ -143,14 +167,16 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
     if str(device) != "cpu":
         torch.cuda.synchronize()
     with open(path, "wb") as f:
-        f.write(MAGIC + struct.pack("<6I", K.ABI_VERSION, C.sizeof(K.Op), prog.n, len(bufs), len(relocs), len(io)))
+        f.write((MAGIC if scale_prog is None else MAGIC_LIVE) + struct.pack("<6I", K.ABI_VERSION, C.sizeof(K.Op), prog.n, len(bufs), len(relocs), len(io)))
+        if scale_prog is not None:
+            f.write(struct.pack("<2I", scale_prog.n, 0))
         for nbytes, kind, _ in bufs:
             f.write(struct.pack("<QII", nbytes, kind, 0))
         for name, b, o, n in io:
             f.write(struct.pack("<24sIIQQ", name.encode(), remap[b], 0, o, n))
         for oi, off, b, o in relocs:
             f.write(struct.pack("<IIIIQ", oi, off, remap[b], 0, o))
-        raw = bytearray(C.string_at(C.addressof(prog.array), prog.n * C.sizeof(K.Op)))
+        raw = bytearray(b"".join(C.string_at(C.addressof(pg.array), pg.n * C.sizeof(K.Op)) for pg in progs))
         for oi, off, _, _ in relocs:             # pointer fields carry no meaning in the file
             p0 = oi * C.sizeof(K.Op) + off
             raw[p0:p0 + 8] = b"\0" * 8
@@ -164,13 +190,13 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
             host = flat.cpu().numpy()
             f.write(host.tobytes())
             data_bytes += nbytes
-    return {"ops": prog.n, "buffers": len(bufs), "relocations": len(relocs), "data_bytes": data_bytes,
+    return {"ops": prog.n, "scale_ops": scale_prog.n if scale_prog is not None else 0, "buffers": len(bufs), "relocations": len(relocs), "data_bytes": data_bytes,
             "scratch_bytes": sum(b[0] for b in bufs if b[1] == 0), "io": {n: sz for n, _, _, sz in io}}
 
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--direction a2b] [--u8 [--canny LOW HIGH]] [--seed N] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH]] [--seed N] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -191,6 +217,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="the program draws 'eps' (and 'noise') itself: seeded noise under the contract of "
                     "i2i_randn_params (include/i2i_turbo.h).  N is the seed saved in the file (step 0); a host sets another by writing four "
                     "uint32 {seed_lo, seed_hi, step, 0} to the buffer named 'seed'")
+    ap.add_argument("--live-scale", action="store_true", help="also store the scale program (per-layer merges, TwinConv fold, their fp32 masters and "
+                    "LoRA factors): a host then moves the LoRA scale / skip gamma with i2i_plan_set_scale() instead of exporting one file per scale")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--base-dir", default=None, help="local stabilityai/sd-turbo snapshot directory")
     ap.add_argument("--pretrained-path", default=None, help="the reference's LoRA checkpoint (.pkl)")
@@ -202,7 +230,7 @@ def main(argv=None):
     if a.canny is not None and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
         ap.error("--canny requires --u8 on a deterministic pix2pix plan (the edge_to_image branch; not with --sketch / --stochastic)")
     H, W = a.size[0], a.size[-1]
-    kw = dict(device=a.device, dtype=dt)
+    kw = dict(device=a.device, dtype=dt, live_scale=a.live_scale)
     if a.lib:
         kw["lib"] = K.Library(a.lib)
     if a.synthetic:
@@ -231,9 +259,9 @@ def main(argv=None):
             plan.set_canny_thresholds(*a.canny)
     if a.seed is not None:
         plan.set_seed(a.seed, 0)
-    info = export_plan(plan, a.out)                 # (re-merges the weights at this plan's r first: plan._prepare)
-    print("wrote %s: %d ops, %d buffers, %.2f GB of weights, %.2f GB of scratch at load; boundary buffers %s"
-          % (a.out, info["ops"], info["buffers"], info["data_bytes"] / 1e9, info["scratch_bytes"] / 1e9, info["io"]))
+    info = export_plan(plan, a.out, live_scale=a.live_scale)                 # (re-merges the weights at this plan's r first: plan._prepare)
+    print("wrote %s: %d ops%s, %d buffers, %.2f GB of weights, %.2f GB of scratch at load; boundary buffers %s"
+          % (a.out, info["ops"], " + %d scale ops" % info["scale_ops"] if a.live_scale else "", info["buffers"], info["data_bytes"] / 1e9, info["scratch_bytes"] / 1e9, info["io"]))
 
 
 if __name__ == "__main__":

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define I2I_ABI_VERSION 12
+#define I2I_ABI_VERSION 13
 
 typedef enum { I2I_F32 = 0, I2I_BF16 = 1, I2I_F16 = 2,
                I2I_U8 = 3   /* only as src_dtype / dst_dtype of the boundary layout ops: uint8 images, HWC interleaved */
@@ -54,7 +54,8 @@ typedef enum {
     I2I_OP_RESIZE_U8 = 13,
     I2I_OP_NOP = 14,           /* one empty kernel launch (bench.py's calibration: microseconds per hipGraph node) */
     I2I_OP_CANNY_U8 = 15,
-    I2I_OP_RANDN = 16
+    I2I_OP_RANDN = 16,
+    I2I_OP_TWIN_FOLD = 17
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -339,6 +340,26 @@ typedef struct {
     int32_t kind;                      /* i2i_randn_kind */
 } i2i_randn_params;
 
+/* TwinConv fold on the device (ABI v13): the sketch model's conv_in, `conv_in_pretrained(x) * (1 - r) + conv_in_curr(x) * r`
+ * (src/pix2pix_turbo.py:16-26), as ONE packed weight tensor written by a kernel, so that a new r costs no host computation and no upload
+ * (with i2i_lora_merge / i2i_merge_group_run it makes r a few bytes of device state: Packer.scale_program).  All operands are packed fp32
+ * as i2i_lora_merge takes them: w_* [N][K], a_* [rank_*][K] with lora_alpha/rank folded in, b_* [N][rank_*]; K a multiple of 4.
+ *   dst[n][k] = cvt( (1-r) * (w_pre[n][k] + r * sum_j b_pre[n][j] * a_pre[j][k]) + r * (w_cur[n][k] + r * sum_j b_cur[n][j] * a_cur[j][k]) )
+ *   bias[n]   = (1-r) * bias_pre[n] + r * bias_cur[n]                         (fp32; bias = NULL: not written)
+ * r = rg[0] on the device (rg = NULL means r = 1; rg[1], the skip gamma, is not used).  Either rank may be 0 (its a / b are then ignored).
+ * ARITHMETIC (fp32, every step one rounding):  s_x = the FMA chain over j in order, from 0, as in i2i_lora_merge;  p_x = fma(r, s_x, w_x);
+ * q = 1 - r, computed once;  dst = cvt(fma(q, p_pre, r * p_cur));  bias = fma(q, bias_pre, r * bias_cur).  So each fp32 element is within
+ * (rank_pre + rank_cur + 4) * 2^-24 * (|w_pre| + |w_cur| + sum |b_pre||a_pre| + sum |b_cur||a_cur|) of the exact value, r = 0 with
+ * rank_pre = 0 stores cvt(w_pre) and r = 1 with rank_cur = 0 stores cvt(w_cur) bit for bit (r in [0, 1]).
+ * Writes dst[0 .. N*K) and bias[0 .. N) only; one launch, no allocation, no synchronisation, graph-capturable. */
+typedef struct {
+    void* dst; float* bias;
+    const float* w_pre; const float* a_pre; const float* b_pre; const float* bias_pre;
+    const float* w_cur; const float* a_cur; const float* b_cur; const float* bias_cur;
+    int32_t N, K, rank_pre, rank_cur;
+    const float* rg;
+} i2i_twin_fold_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -361,6 +382,7 @@ typedef struct {
         i2i_nop_params nop;
         i2i_canny_u8_params canny_u8;
         i2i_randn_params randn;
+        i2i_twin_fold_params twin_fold;
     } u;
 } i2i_op;
 
@@ -394,6 +416,18 @@ int i2i_resize_u8(const i2i_resize_u8_params* p, int dtype, void* stream);   /* 
 int i2i_canny_u8(const i2i_canny_u8_params* p, int dtype, void* stream);     /* dtype ignored (uint8 data); five launches */
 size_t i2i_canny_ws_bytes(int n, int h, int w);                              /* bytes of i2i_canny_u8_params.ws (0 for a non-positive size) */
 int i2i_randn(const i2i_randn_params* p, int dtype, void* stream);           /* dtype ignored (fp32 / uint32 data); one launch */
+int i2i_twin_fold(const i2i_twin_fold_params* p, int dtype, void* stream);   /* one launch */
+
+/* ---- grouped LoRA re-merge (ABI v13): every adapted layer of a network in ONE launch.  `create` checks the n layers as i2i_lora_merge
+ * would (an error names the layer index) and uploads them as a device table with an int32 prefix array of tile counts (synchronous: setup,
+ * not the latency path); `run` is a single launch of a 1-D grid over all tiles -- a workgroup finds its layer by binary search in the
+ * prefix and runs the per-element arithmetic of i2i_lora_merge (the same device function: bit-identical) -- with no allocation and no
+ * synchronisation, graph-capturable.  The table holds copies of the structs: the operands they point at (and rg) must stay alive, their
+ * CONTENTS are read at run time.  Plain layers only: a layer in the LayerNorm-fold form (kscale ..) is refused by `create` and stays a
+ * per-layer i2i_lora_merge after the group (its row sums want one workgroup per row block).  All layers share `dtype`. */
+int i2i_merge_group_create(const i2i_lora_merge_params* layers, int n, int dtype, void** group_out);
+int i2i_merge_group_run(void* group, void* stream);
+int i2i_merge_group_destroy(void* group);
 
 /* ---- calibration micro-kernels (csrc/calib.hip; bench.py's `calib` block: what THIS box delivers on three elementary loads, so that
  * lines measured on different boxes of a pool can be compared).  Not on the forward path. */
@@ -428,6 +462,14 @@ int i2i_plan_read(void* plan, const char* name, void* host_dst, size_t bytes);  
 int i2i_plan_ops(void* plan, const i2i_op** ops, int* n_ops);
 int i2i_plan_run(void* plan, void* stream);
 int i2i_plan_destroy(void* plan);
+/* Live LoRA scale (ABI v13): a file exported with live_scale (magic "I2IPLAN2") also carries the scale program of its packers -- the
+ * per-layer merge ops and the TwinConv fold with their fp32 masters, A, B and the device (r, gamma) pairs.  i2i_plan_set_scale writes
+ * (r, gamma) to every such pair (one small launch on `stream`, ordered after whatever the stream still runs) and enqueues the scale
+ * program on `stream`: one grouped launch for the plain layers, built at load through i2i_merge_group_create, then the remaining ops.  The
+ * next i2i_plan_run on that stream computes at the new scale.  i2i_plan_has_scale: 1 / 0; set_scale on a plan without a scale program
+ * returns I2I_ERR_UNSUPPORTED.  i2i_plan_ops() is the forward alone either way. */
+int i2i_plan_has_scale(void* plan);
+int i2i_plan_set_scale(void* plan, float r, float gamma, void* stream);
 
 #ifdef __cplusplus
 }
