@@ -46,6 +46,7 @@ int dispatch(const i2i_op& op, void* stream) {
         case I2I_OP_CANNY_U8: return i2i_canny_u8(&op.u.canny_u8, op.dtype, stream);
         case I2I_OP_RANDN: return i2i_randn(&op.u.randn, op.dtype, stream);
         case I2I_OP_TWIN_FOLD: return i2i_twin_fold(&op.u.twin_fold, op.dtype, stream);
+        case I2I_OP_SCAN: return i2i_scan(&op.u.scan, op.dtype, stream);
         default: return i2i::fail(I2I_ERR_BAD_ARG, "run: unknown opcode %d", op.opcode);
     }
 }

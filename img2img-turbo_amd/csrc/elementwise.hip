@@ -2,7 +2,10 @@
 //   NCHW <-> NHWC conversion at the .forward() boundary (torch callers hand NCHW; the kernels run NHWC),
 //   DiagonalGaussianDistribution.sample()*scaling_factor + the stochastic mix (src/pix2pix_turbo.py:198,210),
 //   DDPMScheduler.step + /scaling_factor + post_quant_conv (src/pix2pix_turbo.py:200-203),
-//   the seeded Gaussian noise of the callers (torch.manual_seed + torch.randn, src/inference_paired.py:58-60): Philox4x32-10 + Box-Muller.
+//   the seeded Gaussian noise of the callers (torch.manual_seed + torch.randn, src/inference_paired.py:58-60): Philox4x32-10 + Box-Muller,
+//   the numerical health scan of an activation tensor (NaN / Inf / near-saturation counts into a device record; no reference counterpart).
+#include <type_traits>
+
 #include "i2i_dev.h"
 #include "launch.h"
 
@@ -193,6 +196,208 @@ __global__ __launch_bounds__(64) void randn_advance_kernel(uint32_t* state) {
     if (blockIdx.x == 0 && threadIdx.x == 0) state[2] += 1u;
 }
 
+// ---- numerical health scan (the contract is the comment of i2i_scan_params).  Everything is done on bit patterns in the element's OWN
+// format: a = pattern without the sign orders like |x|, a >= INF is Inf / NaN, and the host translates `limit` into the largest pattern
+// `thr` whose value is <= limit (capped at the largest finite one), so "finite and |x| > limit" is a > thr and one unsigned max over a
+// 16-byte chunk decides whether anything in it needs a second look: a healthy chunk costs an AND and a MAX per element.
+constexpr int SCAN_THREADS = 256;       // 4 waves
+constexpr int SCAN_UNROLL = 4;          // independent 16-byte loads per lane and iteration: a workgroup strides over 1024 chunks
+constexpr int SCAN_MAX_GRID = 1024;     // 4 workgroups per CU; with the unroll 16 MiB of loads in flight chip-wide
+
+template <typename T> struct ScanFmt;
+template <> struct ScanFmt<float> { static constexpr uint32_t ABS = 0x7FFFFFFFu, INF = 0x7F800000u, SIGN = 0x80000000u; };
+template <> struct ScanFmt<__bf16> { static constexpr uint32_t ABS = 0x7FFFu, INF = 0x7F80u, SIGN = 0x8000u; };
+template <> struct ScanFmt<_Float16> { static constexpr uint32_t ABS = 0x7FFFu, INF = 0x7C00u, SIGN = 0x8000u; };
+
+// fp32 pattern of a finite non-negative pattern of the element format (exact: integer arithmetic + one exact int -> float conversion)
+template <typename T> __host__ __device__ inline uint32_t scan_widen(uint32_t a);
+template <> __host__ __device__ inline uint32_t scan_widen<float>(uint32_t a) { return a; }
+template <> __host__ __device__ inline uint32_t scan_widen<__bf16>(uint32_t a) { return a << 16; }
+template <> __host__ __device__ inline uint32_t scan_widen<_Float16>(uint32_t a) {
+    const uint32_t e = a >> 10, m = a & 0x3FFu;
+    if (e) return ((e + 112u) << 23) | (m << 13);
+    return __builtin_bit_cast(uint32_t, (float)m * 0x1p-24f);      // subnormal fp16 = m * 2^-24: a normal fp32 number (or 0)
+}
+
+struct ScanAcc { uint32_t nan, pinf, ninf, over, amax; };
+// A row = `head` elements in front of the first 16-byte boundary, `nb` aligned 16-byte chunks, `tail` elements behind them -- the same split
+// for every row (the host sees to that: a contiguous view arrives as ONE row, rows that do not all start on a 16-byte boundary as all tail).
+struct ScanArgs {
+    const char* x; int64_t rows, ld;
+    int64_t head, nb, tail;
+    uint64_t n_elems; uint32_t thr; uint64_t* rec;
+};
+
+template <typename T> __device__ __forceinline__ void scan_elem(uint32_t w, uint32_t thr, ScanAcc& c) {
+    typedef ScanFmt<T> F;
+    const uint32_t a = w & F::ABS;
+    if (a >= F::INF) {
+        if (a > F::INF) ++c.nan;
+        else if (w & F::SIGN) ++c.ninf;
+        else ++c.pinf;
+    } else {
+        c.amax = a > c.amax ? a : c.amax;
+        c.over += a > thr ? 1u : 0u;
+    }
+}
+
+template <typename T> __device__ __forceinline__ void scan_chunk(const u32x4 v, uint32_t thr, ScanAcc& c) {
+    typedef ScanFmt<T> F;
+    uint32_t mx = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (sizeof(T) == 4) {
+            const uint32_t a = v[j] & F::ABS;
+            mx = a > mx ? a : mx;
+        } else {
+            const uint32_t lo = v[j] & F::ABS, hi = (v[j] >> 16) & F::ABS;
+            mx = lo > mx ? lo : mx;
+            mx = hi > mx ? hi : mx;
+        }
+    }
+    if (mx <= thr) {             // thr < INF: nothing here is Inf, NaN or over the limit
+        c.amax = mx > c.amax ? mx : c.amax;
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (sizeof(T) == 4) {
+            scan_elem<T>(v[j], thr, c);
+        } else {
+            scan_elem<T>(v[j] & 0xFFFFu, thr, c);
+            scan_elem<T>(v[j] >> 16, thr, c);
+        }
+    }
+}
+
+// hipcc otherwise waits for the first load before it issues the other three (it hoists the first chunk's arithmetic)
+#ifdef I2I_EMU
+__device__ __forceinline__ void scan_fence(u32x4 (&)[SCAN_UNROLL]) {}
+#else
+__device__ __forceinline__ void scan_fence(u32x4 (&v)[SCAN_UNROLL]) { asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3])); }
+static_assert(SCAN_UNROLL == 4, "scan_fence names four chunks");
+#endif
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, m);
+    return v;
+}
+
+// Two grid-stride loops: the aligned chunks (SCAN_UNROLL independent 16-byte loads per lane, issued together), then the head / tail
+// elements one per lane.  Nothing outside [0, cols) of a row is read.
+// (ONE_ROW: the contiguous view, which is every tensor of a planned forward but one -- no 64-bit division per chunk)
+template <typename T, bool ONE_ROW>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(const ScanArgs a) {
+    constexpr int ESZ = (int)sizeof(T), EPC = 16 / ESZ;
+    typedef typename std::conditional<ESZ == 4, uint32_t, uint16_t>::type word_t;
+    ScanAcc c = {0u, 0u, 0u, 0u, 0u};
+    const int64_t step = (int64_t)gridDim.x * (SCAN_THREADS * SCAN_UNROLL);
+    const int64_t items = a.rows * a.nb;
+    const char* body = a.x + a.head * ESZ;
+    auto chunk_at = [&](int64_t i) -> const u32x4* {
+        if (ONE_ROW) return (const u32x4*)body + i;
+        const int64_t row = i / a.nb, j = i - row * a.nb;
+        return (const u32x4*)(body + row * a.ld * ESZ) + j;
+    };
+    int64_t i0 = (int64_t)blockIdx.x * (SCAN_THREADS * SCAN_UNROLL) + threadIdx.x;
+    for (; i0 + (SCAN_UNROLL - 1) * SCAN_THREADS < items; i0 += step) {
+        u32x4 v[SCAN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SCAN_UNROLL; ++u) v[u] = *chunk_at(i0 + u * SCAN_THREADS);
+        scan_fence(v);      // all loads of the round are issued before the first is consumed
+#pragma unroll
+        for (int u = 0; u < SCAN_UNROLL; ++u) scan_chunk<T>(v[u], a.thr, c);
+    }
+    if (i0 < items) {               // the last, partial round of this lane (the rounds of a lane are SCAN_THREADS apart: at most one is cut)
+        for (int u = 0; u < SCAN_UNROLL - 1; ++u) {
+            const int64_t i = i0 + u * SCAN_THREADS;
+            if (i < items) scan_chunk<T>(*chunk_at(i), a.thr, c);
+        }
+    }
+    const int64_t edge = a.head + a.tail, n_edge = a.rows * edge;
+    for (int64_t i = (int64_t)blockIdx.x * SCAN_THREADS + threadIdx.x; i < n_edge; i += (int64_t)gridDim.x * SCAN_THREADS) {
+        const int64_t row = ONE_ROW ? 0 : i / edge, e = i - row * edge;
+        const int64_t col = e < a.head ? e : e + a.nb * EPC;
+        scan_elem<T>(((const word_t*)a.x)[row * a.ld + col], a.thr, c);
+    }
+    // lanes -> wave (the counts only when some lane of the wave has one) -> workgroup through LDS -> at most one atomic per non-zero field
+    uint32_t amax = c.amax;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = __shfl_xor(amax, m);
+        amax = o > amax ? o : amax;
+    }
+    uint64_t cnt[4] = {c.nan, c.pinf, c.ninf, c.over};
+    if (wave_any((c.nan | c.pinf | c.ninf | c.over) != 0u)) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) cnt[f] = wave_sum_u64(cnt[f]);
+    }
+    uint64_t* red = (uint64_t*)i2i_smem;          // [waves][5]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int f = 0; f < 4; ++f) red[wave * 5 + f] = cnt[f];
+        red[wave * 5 + 4] = amax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t tot[4] = {0, 0, 0, 0}, mx = 0;
+        for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+            for (int f = 0; f < 4; ++f) tot[f] += red[w * 5 + f];
+            mx = red[w * 5 + 4] > mx ? red[w * 5 + 4] : mx;
+        }
+        for (int f = 0; f < 4; ++f)
+            if (tot[f]) agent_add_u64(a.rec + 1 + f, tot[f]);
+        if (mx) agent_max_u64(a.rec + 5, (uint64_t)scan_widen<T>((uint32_t)mx));
+        if (blockIdx.x == 0) {                    // exactly one lane of the launch
+            agent_add_u64(a.rec + 0, 1);
+            if (a.n_elems) agent_add_u64(a.rec + 6, a.n_elems);
+        }
+    }
+}
+
+// largest finite pattern of T's format whose value is <= limit (limit > 0 or +Inf): the patterns order like the values
+template <typename T> uint32_t scan_threshold(float limit) {
+    const uint32_t lb = __builtin_bit_cast(uint32_t, limit);
+    uint32_t lo = 0, hi = ScanFmt<T>::INF - 1;                 // invariant: widen(lo) <= limit
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (scan_widen<T>(mid) <= lb) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+template <typename T> int scan_launch(const i2i_scan_params& p, hipStream_t s) {
+    constexpr int64_t EPC = 16 / (int64_t)sizeof(T);
+    if ((uintptr_t)p.x % sizeof(T)) return i2i::fail(I2I_ERR_BAD_ARG, "scan: x is not aligned to its element type");
+    ScanArgs a;
+    a.x = (const char*)p.x;
+    a.n_elems = (uint64_t)p.rows * (uint64_t)p.cols;
+    a.thr = scan_threshold<T>(p.limit);
+    a.rec = p.rec;
+    int64_t cols = p.cols;
+    a.rows = p.rows, a.ld = p.ld;
+    if (p.ld == p.cols || p.rows <= 1) cols = (int64_t)a.n_elems, a.rows = 1, a.ld = cols;       // contiguous: one long row
+    const int64_t mis = (int64_t)(((uintptr_t)p.x & 15) / sizeof(T));                           // elements past a 16-byte boundary
+    if (a.rows == 1) {
+        a.head = mis ? (EPC - mis < cols ? EPC - mis : cols) : 0;
+        a.nb = (cols - a.head) / EPC, a.tail = cols - a.head - a.nb * EPC;
+    } else if (mis == 0 && a.ld % EPC == 0) {
+        a.head = 0, a.nb = cols / EPC, a.tail = cols % EPC;                                      // every row starts on a 16-byte boundary
+    } else {
+        a.head = 0, a.nb = 0, a.tail = cols;                                                     // element loads throughout
+    }
+    // the grid is sized for the chunk loop (1024 chunks per workgroup and pass), or for the element loop where that one has more to do
+    const int64_t per = SCAN_THREADS * SCAN_UNROLL, w1 = (a.rows * a.nb + per - 1) / per, w2 = (a.rows * (a.head + a.tail) + per - 1) / per;
+    const int64_t want = w1 > w2 ? w1 : w2;
+    const unsigned g = (unsigned)(want < 1 ? 1 : (want > SCAN_MAX_GRID ? SCAN_MAX_GRID : want));
+    const size_t smem = (SCAN_THREADS / 64) * 5 * sizeof(uint64_t);
+    if (a.rows == 1) hipLaunchKernelGGL((scan_kernel<T, true>), dim3(g), dim3(SCAN_THREADS), smem, s, a);
+    else hipLaunchKernelGGL((scan_kernel<T, false>), dim3(g), dim3(SCAN_THREADS), smem, s, a);
+    return i2i::check_launch("scan");
+}
+
 inline unsigned grid_for(int64_t n) {
     const int64_t b = (n + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -319,4 +524,18 @@ extern "C" int i2i_randn(const i2i_randn_params* p, int /*dtype*/, void* stream)
     if (p->kind == I2I_RANDN_NORMAL) hipLaunchKernelGGL((randn_kernel<true>), dim3(g), dim3(256), 0, s, *p);
     else hipLaunchKernelGGL((randn_kernel<false>), dim3(g), dim3(256), 0, s, *p);
     return i2i::check_launch("randn");
+}
+
+extern "C" int i2i_scan(const i2i_scan_params* p, int dtype, void* stream) {
+    if (!p || !p->x || !p->rec) return i2i::fail(I2I_ERR_BAD_ARG, "scan: null pointer");
+    if (!(p->limit > 0.f)) return i2i::fail(I2I_ERR_BAD_ARG, "scan: limit must be > 0");      // (a NaN limit fails the comparison too)
+    if (p->rows < 0 || p->cols < 0 || p->ld < p->cols) return i2i::fail(I2I_ERR_BAD_ARG, "scan: rows = %lld, cols = %d, ld = %lld", (long long)p->rows, p->cols, (long long)p->ld);
+    if ((uintptr_t)p->rec & 63) return i2i::fail(I2I_ERR_BAD_ARG, "scan: rec is not 64-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    switch (dtype) {
+        case I2I_F32: return scan_launch<float>(*p, s);
+        case I2I_BF16: return scan_launch<__bf16>(*p, s);
+        case I2I_F16: return scan_launch<_Float16>(*p, s);
+        default: return i2i::fail(I2I_ERR_BAD_ARG, "scan: dtype %d is not a float type", dtype);
+    }
 }

@@ -139,6 +139,15 @@ __device__ __forceinline__ int32_t agent_min_i32(int32_t* p, int32_t v) {     //
 __device__ __forceinline__ int32_t agent_load_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ int32_t agent_min_i32(int32_t* p, int32_t v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
+// no-return forms on 64-bit words (the record of the health scan, elementwise.hip): integer add / unsigned max commute, so the result does
+// not depend on the order the workgroups arrive in
+#ifdef I2I_EMU
+__device__ __forceinline__ void agent_add_u64(uint64_t* p, uint64_t v) { *p += v; }
+__device__ __forceinline__ void agent_max_u64(uint64_t* p, uint64_t v) { if (v > *p) *p = v; }
+#else
+__device__ __forceinline__ void agent_add_u64(uint64_t* p, uint64_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void agent_max_u64(uint64_t* p, uint64_t v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#endif
 
 // ---- arithmetic of the seeded noise op (randn_kernel, elementwise.hip): the high half of a 32 x 32 bit product (v_mul_hi_u32) and the
 // pi-scaled trigonometric functions (exact argument reduction: no fp32 product with pi).  The host has neither: the emulator reduces

@@ -96,6 +96,7 @@ const std::vector<size_t>& ptr_fields(int opcode) {
     static const std::vector<size_t> twin = {PF(twin_fold, dst), PF(twin_fold, bias), PF(twin_fold, w_pre), PF(twin_fold, a_pre), PF(twin_fold, b_pre),
                                              PF(twin_fold, bias_pre), PF(twin_fold, w_cur), PF(twin_fold, a_cur), PF(twin_fold, b_cur), PF(twin_fold, bias_cur),
                                              PF(twin_fold, rg)};
+    static const std::vector<size_t> scan = {PF(scan, x), PF(scan, rec)};
     switch (opcode) {
         case I2I_OP_IGEMM: return igemm;
         case I2I_OP_GN_STATS: return gn_stats;
@@ -113,6 +114,7 @@ const std::vector<size_t>& ptr_fields(int opcode) {
         case I2I_OP_CANNY_U8: return canny;
         case I2I_OP_RANDN: return randn;
         case I2I_OP_TWIN_FOLD: return twin;
+        case I2I_OP_SCAN: return scan;
         default: return none;
     }
 }

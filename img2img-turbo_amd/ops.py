@@ -179,6 +179,15 @@ def twin_fold(dst, bias, pre, cur, rg, *, bias_pre=None, bias_cur=None):
     return K.OP_TWIN_FOLD, _keep(p, dst, bias, w0, a0, b0, bias_pre, w1, a1, b1, bias_cur, rg)
 
 
+def scan(x, rec, *, rows, cols, ld=None, limit):
+    """rec[0..7] (a 64-byte aligned slice of an int64 tensor holding uint64 bits) += the health record of the rows x cols view of ``x`` (the
+    contract: i2i_scan_params, include/i2i_turbo.h).  The op's dtype must be the element type of ``x``."""
+    p = K.ScanParams()
+    p.x, p.rec = ptr(x), ptr(rec)
+    p.rows, p.cols, p.ld, p.limit = int(rows), int(cols), int(cols if ld is None else ld), float(limit)
+    return K.OP_SCAN, _keep(p, x, rec)
+
+
 def nhwc_to_nchw(x, y, *, n, c, h, w, ldx, clamp=0, mul=0.0, add=0.0):
     """y: NCHW float tensor, or a uint8 HWC image batch [n, h, w, c] (then y = trunc(clamp01(x*mul+add)*255))."""
     p = K.NhwcToNchwParams()

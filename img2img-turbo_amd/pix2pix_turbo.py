@@ -65,15 +65,23 @@ class TurboGeneratorBase(torch.nn.Module):
     MAX_PLANS = 8          # distinct (batch, size, mode) programs kept alive; each owns an activation pool + a hipGraph
 
     def __init__(self, weights: GeneratorWeights, device="cuda", dtype=torch.float32, lib=None,
-                 tokenizer=None, text_encoder=None, use_graph=True, fuse_gn=True, flash=True, plan_options=None, unet_dtype=None, live_scale=False):
+                 tokenizer=None, text_encoder=None, use_graph=True, fuse_gn=True, flash=True, plan_options=None, unet_dtype=None, live_scale=False,
+                 health=None, health_limit=None):
         """``dtype``: element type of activations and packed weights (fp32 = the exact-MFMA parity mode).  ``unet_dtype``: another 16-bit
         type for the UNet alone -- ``dtype=torch.bfloat16, unet_dtype=torch.float16`` keeps the VAE (whose real activations overflow fp16)
         in bf16 and gives the UNet, whose error the 1-step scheduler multiplies by 14.6, fp16's three extra mantissa bits.
         ``live_scale=True``: ``set_lora_scale(r)`` writes the device pair (r, gamma) and runs each packer's scale program
         (Packer.scale_program: one grouped merge launch, the LayerNorm-fold layers, the TwinConv fold as a kernel) -- asynchronous on the
         stream with no host tensor math.  Off (the default), the per-layer loop and the host TwinConv fold run as before; the device fold
-        rounds differently from torch's host fold, so a TwinConv checkpoint's outputs differ in the last bits between the two settings."""
+        rounds differently from torch's host fold, so a TwinConv checkpoint's outputs differ in the last bits between the two settings.
+        ``health="stages"`` / ``"all"``: every plan carries numerical health scans (ForwardPlan(health=...), the contract of i2i_scan_params) --
+        per-stage NaN / Inf / near-saturation counts accumulated on the device; read them with ``health_report()`` /
+        ``health_first_bad()``, zero them with ``health_reset()``.  ``forward`` itself never synchronises for it; off (None) nothing changes.
+        ``health_limit``: the near-saturation threshold (default: half the largest finite value of each scanned tensor's dtype)."""
         super().__init__()
+        assert health in (None, "stages", "all"), health
+        self.health, self.health_limit = health, health_limit
+        self._last_plan = None
         self.live_scale = bool(live_scale)
         self.unet_dtype_ = unet_dtype
         self.weights = weights
@@ -123,6 +131,27 @@ class TurboGeneratorBase(torch.nn.Module):
         for plan in self._plans.values():
             plan.release()
         self._plans.clear()
+        self._last_plan = None
+
+    # ---- numerical health (of the plan that ran most recently) ----
+    def _health_plan(self):
+        if not self.health:
+            raise _capi.I2IError("health scans are off: construct the model with health=\"stages\" or \"all\"")
+        if self._last_plan is None or self._last_plan.released:
+            raise _capi.I2IError("no forward has run yet (or its plan was released)")
+        return self._last_plan
+
+    def health_report(self):
+        """One dict per scanned tensor of the most recently run plan, in program order (ForwardPlan.health_report; synchronises)."""
+        return self._health_plan().health_report()
+
+    def health_first_bad(self):
+        """The first tensor, in program order, that held a NaN or an Inf since the last reset, or None (synchronises)."""
+        return self._health_plan().health_first_bad()
+
+    def health_reset(self):
+        """Zero the records of the most recently run plan (asynchronous on the current stream)."""
+        self._health_plan().health_reset()
 
     # ---- plumbing ----
     def _on_device(self):
@@ -169,7 +198,8 @@ class TurboGeneratorBase(torch.nn.Module):
         after every run; again only the boolean is part of the key, every seed shares the plan."""
         r_plan = float(r) if stochastic else 1.0
         self.set_lora_scale(r_plan)
-        key = (B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((True,) if canny else ()) + (("rng",) if rng else ())
+        key = ((B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((True,) if canny else ()) + (("rng",) if rng else ())
+               + (("health", self.health, self.health_limit) if self.health else ()))
         if key in self._plans:
             self._plans.move_to_end(key)
         else:
@@ -180,6 +210,8 @@ class TurboGeneratorBase(torch.nn.Module):
                 opts["canny"] = True
             if rng:
                 opts["rng"] = True
+            if self.health:
+                opts["health"], opts["health_limit"] = self.health, self.health_limit
             with self._on_device():
                 self._plans[key] = ForwardPlan(self.lib, self.weights, B, H, W, self.dtype_, self.device_, stochastic=stochastic,
                                                r=self._r, direction=direction, ctx_batch=ctx_batch, fuse_gn=self.fuse_gn,
@@ -232,6 +264,7 @@ class TurboGeneratorBase(torch.nn.Module):
                 plan.replay()
             else:
                 plan.run()
+            self._last_plan = plan
             return plan.out.clone()
 
 

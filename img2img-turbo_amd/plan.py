@@ -75,7 +75,7 @@ class ForwardPlan:
 
     def __init__(self, lib, weights, B, H, W, dtype, device, *, stochastic=False, r=1.0, direction="a2b",
                  ctx_batch=1, fuse_gn=True, flash=True, out_dtype=None, packers=None, debug=False, dma_small=True, fuse_gn_stats=True, subpix=True, halo_min_tiles=160, u8_io=None, fuse_vae_attention=True,
-                 unet_dtype=None, canny=False, rng=False):
+                 unet_dtype=None, canny=False, rng=False, health=None, health_limit=None):
         assert H % 8 == 0 and W % 8 == 0, "input must be a multiple of 8 (src/inference_paired.py:38-41)"
         # H, W multiples of 8 suffice (src/inference_paired.py:38-41): latent sizes that are not multiples of 8 make the
         # UNet levels odd (70 -> 35 -> 18 -> 9), handled like diffusers' forward_upsample_size path (explicit sizes).
@@ -104,6 +104,16 @@ class ForwardPlan:
         self.pool = Pool(device)
         self.pool.no_reuse = debug
         self.taps = {}          # label -> Act of that op's output (meaningful with debug=True)
+        # health: None | "stages" | "all" -- numerical health scans (I2I_OP_SCAN, the contract of i2i_scan_params in include/i2i_turbo.h) recorded
+        # in program order right behind the producer, while its pooled buffer is live (no debug=True needed): "all" = the output of every op
+        # registered in `taps` (the convolutions) plus the stage boundaries, "stages" = the boundaries alone (STAGE names below: each
+        # encoder / UNet / decoder block's output, moments, latents, the eps-prediction, the decoder's input, the tensor in front of the
+        # clamp).  A boundary tensor that a convolution has just written is scanned under both labels in "all".  Each scan runs in the dtype
+        # of the tensor it reads; record i of `health_rec` (uint64 [n_taps][8]) belongs to health_labels[i], accumulated until health_reset().
+        assert health in (None, "stages", "all"), health
+        self.health, self.health_limit = health, (None if health_limit is None else float(health_limit))
+        self.health_labels, self.health_taps, self.health_rec = [], [], None      # health_taps[i] = (tensor, rows, cols, ld) of record i
+        self._health_ops = []
         self.prog = K.Program()
         self.op_flops = []      # algorithmic FLOPs per op (2*MAC), parallel to prog.ops
         self.op_flops_exec = [] # FLOPs the matrix pipe executes for the op (sub-pixel upsamplers: 4/9 of the 3x3 part), parallel to prog.ops
@@ -175,6 +185,7 @@ class ForwardPlan:
                     torch.zeros(B, 3, H, W, dtype=self.out_dtype, device=device))
         self._build()
         self._finish_gn_scratch()
+        self._finish_health()
         self.prog.freeze()
         self.graph = None
 
@@ -210,6 +221,74 @@ class ForwardPlan:
         for i, (_opc, _dt, p, _label) in enumerate(self.prog.ops):
             if p is params:
                 self.op_kernel[i] = kernel
+
+    # ------------------------------------------------------------------ health scans
+    HEALTH_LIMIT = {torch.float32: float(torch.finfo(torch.float32).max) / 2, torch.bfloat16: float(torch.finfo(torch.bfloat16).max) / 2,
+                    torch.float16: float(torch.finfo(torch.float16).max) / 2}     # default: half the largest finite value of the dtype
+
+    def _scan(self, label, t, rows, cols, ld=None):
+        """Record one scan of the rows x cols view of tensor ``t`` (its own dtype); the record pointer is patched in _finish_health."""
+        limit = self.health_limit if self.health_limit is not None else self.HEALTH_LIMIT[t.dtype]
+        op = O.scan(t, None, rows=rows, cols=cols, ld=ld, limit=limit)
+        with self._as(t.dtype):
+            self._add(op, "health: " + label, kernel="scan_kernel", nbytes=rows * cols * t.element_size())
+        self._health_ops.append(op[1])
+        self.health_labels.append(label)
+        self.health_taps.append((t, rows, cols, cols if ld is None else ld))
+
+    def _tap(self, label, a: Act, cols=None):
+        """A tensor registered in `taps` (health="all")."""
+        if self.health == "all":
+            self._scan(label, a.t, a.n * a.hw, cols or a.c, a.c)
+
+    def _stage(self, label, a, cols=None, rows=None):
+        """A stage boundary (both modes).  ``a``: an Act, or a flat tensor with ``rows`` / ``cols``."""
+        if self.health is None:
+            return
+        if isinstance(a, Act):
+            self._scan(label, a.t, a.n * a.hw, cols or a.c, a.c)
+        else:
+            self._scan(label, a, rows, cols)
+
+    def _finish_health(self):
+        if self.health is None:
+            return
+        n = len(self._health_ops)
+        self._health_i64 = torch.zeros(max(n, 1), 8, dtype=torch.int64, device=self.device)      # (torch fills / copies int64; the kernel sees uint64)
+        assert self._health_i64.data_ptr() % 64 == 0
+        self.health_rec = self._health_i64.view(torch.uint64)[:n]
+        for i, p in enumerate(self._health_ops):
+            p.rec = self._health_i64.data_ptr() + 64 * i
+            p._keep = tuple(p._keep) + (self._health_i64,)
+        self.health_names = torch.tensor(list(b"".join(l.encode() + b"\0" for l in self.health_labels)) or [0], dtype=torch.uint8, device=self.device)
+
+    def health_reset(self):
+        """Zero every record (a fill on the current stream; asynchronous)."""
+        assert self.health, "this plan has no health scans (ForwardPlan(health=...))"
+        with self._on_device():
+            self._health_i64.zero_()
+
+    def health_report(self):
+        """Synchronise and return one dict per tap, in program order: label, dtype, runs, n_nan, n_pos_inf, n_neg_inf, n_over, max_abs
+        (a float: the largest finite |x|), elements -- accumulated over every run / replay since the last health_reset()."""
+        assert self.health, "this plan has no health scans (ForwardPlan(health=...))"
+        import numpy as np
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(self.device)
+        rec = self._health_i64.cpu().numpy().view(np.uint64)
+        out = []
+        for i, (label, (t, _r, _c, _ld)) in enumerate(zip(self.health_labels, self.health_taps)):
+            r = [int(v) for v in rec[i]]
+            out.append(dict(label=label, dtype=str(t.dtype).replace("torch.", ""), runs=r[0], n_nan=r[1], n_pos_inf=r[2], n_neg_inf=r[3], n_over=r[4],
+                            max_abs=float(np.array([r[5]], dtype=np.uint32).view(np.float32)[0]), elements=r[6]))
+        return out
+
+    def health_first_bad(self):
+        """The first tap, in program order, that saw a NaN or an Inf (its report dict), or None."""
+        for d in self.health_report():
+            if d["n_nan"] or d["n_pos_inf"] or d["n_neg_inf"]:
+                return d
+        return None
 
     @property
     def esz(self):
@@ -530,6 +609,7 @@ class ForwardPlan:
         nb = (x.n * hin * win * (x.c + c1) + x.n * ho * wo * out.c) * self.esz if kname.startswith("conv_narrow") else 0
         self._add(op, label, fl, kernel=kname, flops_exec=fl_exec, nbytes=nb)
         self.taps[label] = out
+        self._tap(label, out, cols=n_out if n_out != out.c else None)
         if gn and not fused:
             self.free(x_in0)
         self.flops += fl
@@ -884,6 +964,7 @@ class ForwardPlan:
                 self.free(cur)
                 cur = nxt
             h = cur
+            self._stage(f"encoder.down_blocks.{i}", h)
         m = self.resnet(pk, "encoder.mid_block.resnets.0", h, boc[-1], g, eps)
         self.free(h)                                          # down3 output is not a skip
         m2 = self.vae_attention(pk, "encoder.mid_block.attentions.0", m, g, eps)
@@ -892,6 +973,7 @@ class ForwardPlan:
         self.free(m2)
         moments = self.conv(pk.encoder_out(), m3, gn=(pk, "encoder.conv_norm_out", g, eps), act=1, out_f32=1, label="encoder.conv_out+quant_conv")
         self.free(m3)
+        self._stage("moments", moments, cols=2 * a.latent_channels)
         return moments, skips
 
     def _unet(self, u: Act) -> Act:
@@ -914,11 +996,13 @@ class ForwardPlan:
             if i < nb - 1:
                 h = self.conv(pk.conv(f"down_blocks.{i}.downsamplers.0.conv"), h, stride=2, label=f"down_blocks.{i}.downsamplers.0.conv")
                 res.append(h)
+            self._stage(f"unet.down_blocks.{i}", h)
         m = self.resnet(pk, "mid_block.resnets.0", h, boc[-1], g, eps, arch=a)
         m2 = self.transformer(pk, "mid_block.attentions.0", m, heads[-1], g)
         self.free(m)
         h = self.resnet(pk, "mid_block.resnets.1", m2, boc[-1], g, eps, arch=a)
         self.free(m2)
+        self._stage("unet.mid_block", h)
         rheads = list(reversed(heads))
         rboc = list(reversed(boc))
         for i, c in enumerate(rboc):
@@ -937,9 +1021,11 @@ class ForwardPlan:
                 h2 = self.upsample_conv(pk, f"up_blocks.{i}.upsamplers.0.conv", h, f"up_blocks.{i}.upsamplers.0.conv", size=(nxt.h, nxt.w))
                 self.free(h)
                 h = h2
+            self._stage(f"unet.up_blocks.{i}", h)
         assert not res
         e = self.conv(pk.conv("conv_out"), h, gn=(pk, "conv_norm_out", g, eps), act=1, out_f32=1, label="conv_out")     # eps-prediction kept fp32
         self.free(h)
+        self._stage("eps_prediction", e, cols=self.va.latent_channels)
         return e
 
     def _vae_decoder(self, z: Act, skips: List[Act]) -> Act:
@@ -973,8 +1059,10 @@ class ForwardPlan:
                 skip_done = bool(getattr(h2, "k2_fused", False))
                 self.free(h)
                 h = h2
+            self._stage(f"decoder.up_blocks.{i}", h)
         y = self.conv(pk.conv("decoder.conv_out"), h, gn=(pk, "decoder.conv_norm_out", g, eps), act=1, label="decoder.conv_out")
         self.free(h)
+        self._stage("pre_clamp", y, cols=3)
         return y
 
     def _build(self):
@@ -1006,6 +1094,7 @@ class ForwardPlan:
             self._add(O.posterior(moments.t, self.eps, u.t, n=B, hw=h8 * w8, lat=lat, ldm=moments.c, ldu=8, sf=sf, r=self.r,
                                   r_dev=self.pv.rg if self.stochastic else None,
                                   noise=self.noise, noise_n=B, u_f32=self.u32, moments_f32=1), "posterior_sample")
+            self._stage("latents", self.u32, rows=B * h8 * w8, cols=lat)
             self.free(moments)
             e = self._unet(u)
             self.free(u)
@@ -1014,6 +1103,7 @@ class ForwardPlan:
         z = self.new(B, h8, w8, 8)
         self._add(O.ddpm_postquant(self.u32, e.t, z.t, wpq, bpq, n=B, hw=h8 * w8, lat=lat, ldu=lat, lde=e.c, ldy=8,
                                    sqrt_abar=sa, sqrt_1m_abar=s1, sf=sf, u_f32=1, e_f32=1), "ddpm_step+post_quant")
+        self._stage("post_quant", z, cols=lat)     # (x0 itself lives in registers only: the decoder's input is the first tensor behind it)
         self.free(e)
         y = self._vae_decoder(z, skips)
         self.free(z)

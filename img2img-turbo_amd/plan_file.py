@@ -14,7 +14,9 @@ merged at the current scale, norm parameters, device scalars, ticket counters --
 names: "x", "ctx", "eps", "noise" (stochastic plans), "out", and "canny_thr" (plans with the Canny op in front: two int32 {low, high},
 saved with the values of the export, which a host overwrites with i2i_plan_write to move the thresholds), and "seed" (plans that draw
 their own noise, --seed N: the 16-byte state {seed_lo, seed_hi, step, reserved} of i2i_randn_params, saved with the exported seed at step 0;
-the program overwrites "eps" / "noise", which a host may read back, and advances the step after every run).
+the program overwrites "eps" / "noise", which a host may read back, and advances the step after every run), and "health" / "health_names"
+(plans built with health=: the n_taps x 8 uint64 records of the scans, saved zeroed and accumulated by every run, and the n_taps labels as
+NUL-terminated bytes -- io names are 24 bytes, so the labels travel as data; examples/health_host.c prints them).
 
 This replaces the reference's ``model(...)`` call (src/pix2pix_turbo.py:186-219, src/cyclegan_turbo.py:241-254) for hosts that are not
 Python; the planner itself (route queries, tile choices, buffer recycling) stays in plan.py and runs once, at export.
@@ -71,7 +73,8 @@ def export_plan(plan, path, extra_tensors=(), live_scale=False):
 
     The packed weights are SHARED by every plan of a model and hold whatever LoRA / skip scale ``r`` was merged last (another plan's
     ``r``, or 1.0 after a deterministic plan ran): ``plan._prepare()`` re-merges them at THIS plan's ``r`` before anything is read
-    back, and refuses a plan whose buffers were released (plan-cache eviction)."""
+    back, and refuses a plan whose buffers were released (plan-cache eviction).  A plan with health scans is exported with zeroed records:
+    ``plan.health_reset()`` runs first, so read ``health_report()`` before exporting if the counts matter."""
     plan._prepare()
     named = {"x": plan.x_in, "ctx": plan.ctx, "eps": plan.eps, "out": plan.out}
     if getattr(plan, "noise", None) is not None:
@@ -82,10 +85,13 @@ def export_plan(plan, path, extra_tensors=(), live_scale=False):
         named["canny_thr"] = plan.canny_thr
     if getattr(plan, "rng", False):
         named["seed"] = plan.rng_state
+    if getattr(plan, "health", None):       # the records (zeroed in the file: a loaded plan starts counting at 0) and their labels, NUL-separated
+        plan.health_reset()
+        named["health"], named["health_names"] = plan._health_i64, plan.health_names
     gn_scratch = [t for t in (getattr(plan, n, None) for n in ("gn_partial", "gn_ss", "gn_counters")) if t is not None]
     if getattr(plan, "canny", False):
         gn_scratch += [plan.canny_edges, plan.canny_ws]
-    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed"), holders=[plan] + list(extra_tensors), device=plan.device,
+    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed", "health", "health_names"), holders=[plan] + list(extra_tensors), device=plan.device,
                           scale_prog=scale_program_of(plan) if live_scale else None)
 
 
@@ -196,7 +202,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH]] [--seed N] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH]] [--seed N] [--health stages|all] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -217,6 +223,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="the program draws 'eps' (and 'noise') itself: seeded noise under the contract of "
                     "i2i_randn_params (include/i2i_turbo.h).  N is the seed saved in the file (step 0); a host sets another by writing four "
                     "uint32 {seed_lo, seed_hi, step, 0} to the buffer named 'seed'")
+    ap.add_argument("--health", default=None, choices=["stages", "all"], help="numerical health scans in the program (ForwardPlan(health=...)): the file "
+                    "gets the buffers 'health' (8 uint64 per scanned tensor, accumulated by every run) and 'health_names' (their labels)")
     ap.add_argument("--live-scale", action="store_true", help="also store the scale program (per-layer merges, TwinConv fold, their fp32 masters and "
                     "LoRA factors): a host then moves the LoRA scale / skip gamma with i2i_plan_set_scale() instead of exporting one file per scale")
     ap.add_argument("--device", default="cuda:0")
@@ -230,7 +238,7 @@ def main(argv=None):
     if a.canny is not None and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
         ap.error("--canny requires --u8 on a deterministic pix2pix plan (the edge_to_image branch; not with --sketch / --stochastic)")
     H, W = a.size[0], a.size[-1]
-    kw = dict(device=a.device, dtype=dt, live_scale=a.live_scale)
+    kw = dict(device=a.device, dtype=dt, live_scale=a.live_scale, health=a.health)
     if a.lib:
         kw["lib"] = K.Library(a.lib)
     if a.synthetic:

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define I2I_ABI_VERSION 13
+#define I2I_ABI_VERSION 14
 
 typedef enum { I2I_F32 = 0, I2I_BF16 = 1, I2I_F16 = 2,
                I2I_U8 = 3   /* only as src_dtype / dst_dtype of the boundary layout ops: uint8 images, HWC interleaved */
@@ -55,7 +55,8 @@ typedef enum {
     I2I_OP_NOP = 14,           /* one empty kernel launch (bench.py's calibration: microseconds per hipGraph node) */
     I2I_OP_CANNY_U8 = 15,
     I2I_OP_RANDN = 16,
-    I2I_OP_TWIN_FOLD = 17
+    I2I_OP_TWIN_FOLD = 17,
+    I2I_OP_SCAN = 18
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -360,6 +361,35 @@ typedef struct {
     const float* rg;
 } i2i_twin_fold_params;
 
+/* Numerical health scan (ABI v14): counts of what left the number format in one activation tensor, accumulated into a 64-byte device
+ * record -- the answer to "which stage of a 16-bit forward first produced a NaN / Inf, and how close to the limit were the others?"
+ * without a read-back of the tensor, a synchronisation, or debug buffers (the planner places the op right behind the producer, while
+ * the pooled buffer is live: ForwardPlan(health=...)).  A pure read of x; nothing but `rec` is written.
+ *   VIEW     rows x cols elements of the op's dtype (I2I_F32 / I2I_BF16 / I2I_F16), row r at x + r * ld (ld >= cols, in elements).
+ *            Elements [cols, ld) of a row are NOT read, whatever they hold.  x needs the alignment of its element type only.
+ *   RECORD   eight uint64, 64-byte aligned, ACCUMULATED by every launch until the owner zeroes them:
+ *              [0] runs        +1 per launch
+ *              [1] n_nan       exponent all ones, mantissa != 0 (any payload, either sign)
+ *              [2] n_pos_inf   [3] n_neg_inf
+ *              [4] n_over      finite and |x| > limit (strict; limit is fp32, the comparison is exact)
+ *              [5] max_abs     the fp32 bit pattern of the largest finite |x| seen (0 if none; bf16 / fp16 widen exactly, -0 counts as 0),
+ *                              updated with an unsigned max: non-negative fp32 patterns order like their values
+ *              [6] elements    +rows * cols per launch
+ *              [7] reserved    stays 0
+ *   Every update is an integer add or an unsigned max: the record is bit-identical for any grid, any workgroup order, and between
+ *   the CPU emulator and the GPU (tests/health_ref.py is the CPU oracle of this text).  No float atomics.
+ * One launch (capped grid, grid-stride loop, 16-byte loads per lane on the 16-byte aligned part of every row, element loads on the
+ * rest), no allocation, no synchronisation, no read-back; graph-capturable.  Partial results are reduced lanes -> wave -> workgroup
+ * (LDS) and a workgroup issues at most one agent-scope atomic per NON-ZERO field: a healthy tensor costs one max per workgroup.
+ * Errors (I2I_ERR_BAD_ARG): null params / x / rec, limit not > 0 (NaN included), negative sizes, ld < cols, rec not 64-byte aligned,
+ * x not aligned to its element, a dtype other than the three float types (I2I_U8 included). */
+typedef struct {
+    const void* x;
+    int64_t rows; int32_t cols; int64_t ld;
+    float limit;                       /* "near saturation" threshold, > 0 (the planner's default: half the dtype's largest finite value) */
+    uint64_t* rec;                     /* the 8 x uint64 record above */
+} i2i_scan_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -383,6 +413,7 @@ typedef struct {
         i2i_canny_u8_params canny_u8;
         i2i_randn_params randn;
         i2i_twin_fold_params twin_fold;
+        i2i_scan_params scan;
     } u;
 } i2i_op;
 
@@ -417,6 +448,7 @@ int i2i_canny_u8(const i2i_canny_u8_params* p, int dtype, void* stream);     /* 
 size_t i2i_canny_ws_bytes(int n, int h, int w);                              /* bytes of i2i_canny_u8_params.ws (0 for a non-positive size) */
 int i2i_randn(const i2i_randn_params* p, int dtype, void* stream);           /* dtype ignored (fp32 / uint32 data); one launch */
 int i2i_twin_fold(const i2i_twin_fold_params* p, int dtype, void* stream);   /* one launch */
+int i2i_scan(const i2i_scan_params* p, int dtype, void* stream);             /* one launch; dtype = element type of x */
 
 /* ---- grouped LoRA re-merge (ABI v13): every adapted layer of a network in ONE launch.  `create` checks the n layers as i2i_lora_merge
  * would (an error names the layer index) and uploads them as a device table with an int32 prefix array of tile counts (synchronous: setup,
@@ -453,7 +485,9 @@ int i2i_graph_destroy(void* graph);
  * (src/pix2pix_turbo.py:186-219) is for a Python host, for one fixed (batch, size, dtype, mode).  Names of the pix2pix / CycleGAN plans:
  * "x" (fp32 NCHW images in [-1, 1], or uint8 NHWC with the u8 boundary), "ctx" ([1 | B][77][1024] text states in the plan's dtype),
  * "eps" (fp32 [B][4][H/8][W/8] posterior noise), "noise" (stochastic plans), "out" (images, NCHW in the plan's output dtype or uint8 NHWC);
- * plans exported with a seed also have "seed" (16 bytes: the i2i_randn_params state; the program then fills "eps" / "noise" itself).
+ * plans exported with a seed also have "seed" (16 bytes: the i2i_randn_params state; the program then fills "eps" / "noise" itself);
+ * plans built with health= also have "health" (n_taps x 8 uint64: the i2i_scan_params records in program order, accumulated over the runs;
+ * zero them with i2i_plan_write) and "health_names" (the n_taps labels, each NUL-terminated, as bytes): examples/health_host.c.
  * load / write / read are synchronous; run only enqueues (i2i_run); i2i_plan_ops() hands the program to i2i_graph_create(). */
 int i2i_plan_load(const char* path, void** plan_out);
 int i2i_plan_io(void* plan, const char* name, void** dev_ptr, size_t* bytes);       /* device address + size of a named buffer */
