@@ -21,6 +21,8 @@ OP_CANNY_U8 = 15
 OP_RANDN = 16
 OP_TWIN_FOLD = 17
 OP_SCAN = 18
+OP_RANDN_BATCH = 19      # ABI 14 additions: new opcodes / structs / exports only, so the version number did not move (include/i2i_turbo.h)
+OP_CANNY_U8_BATCH = 20
 RANDN_NORMAL, RANDN_RAW, RANDN_ADVANCE = 0, 1, 2      # i2i_randn_kind
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -115,6 +117,14 @@ class RandnParams(C.Structure):
     _fields_ = [("dst", vp), ("n", i64), ("state", vp), ("seed", C.c_uint64), ("step", C.c_uint32), ("stream_id", C.c_uint32), ("kind", i32)]
 
 
+class RandnBatchParams(C.Structure):
+    _fields_ = [("dst", vp), ("per_image", i64), ("batch", i32), ("states", vp), ("stream_id", C.c_uint32), ("kind", i32)]
+
+
+class CannyU8BatchParams(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("n", i32), ("h", i32), ("w", i32), ("c", i32), ("out_c", i32), ("thr", vp), ("ws", vp)]
+
+
 class TwinFoldParams(C.Structure):
     _fields_ = [("dst", vp), ("bias", vp), ("w_pre", vp), ("a_pre", vp), ("b_pre", vp), ("bias_pre", vp),
                 ("w_cur", vp), ("a_cur", vp), ("b_cur", vp), ("bias_cur", vp),
@@ -134,7 +144,8 @@ class _OpUnion(C.Union):
                 ("layernorm", LayerNormParams), ("softmax", SoftmaxParams), ("attention", AttentionParams),
                 ("to_nhwc", NchwToNhwcParams), ("to_nchw", NhwcToNchwParams), ("embed", EmbedParams),
                 ("posterior", PosteriorParams), ("ddpm", DdpmParams), ("lora_merge", LoraMergeParams), ("resize_u8", ResizeU8Params),
-                ("nop", NopParams), ("canny_u8", CannyU8Params), ("randn", RandnParams), ("twin_fold", TwinFoldParams), ("scan", ScanParams)]
+                ("nop", NopParams), ("canny_u8", CannyU8Params), ("randn", RandnParams), ("twin_fold", TwinFoldParams), ("scan", ScanParams),
+                ("randn_batch", RandnBatchParams), ("canny_u8_batch", CannyU8BatchParams)]
 
 
 class Op(C.Structure):
@@ -144,11 +155,13 @@ class Op(C.Structure):
 _FIELD_OF = {OP_IGEMM: "igemm", OP_GN_STATS: "gn_stats", OP_GN_APPLY: "gn_apply", OP_LAYERNORM: "layernorm",
              OP_SOFTMAX: "softmax", OP_ATTENTION: "attention", OP_NCHW_TO_NHWC: "to_nhwc",
              OP_NHWC_TO_NCHW: "to_nchw", OP_POSTERIOR: "posterior", OP_DDPM_POSTQUANT: "ddpm", OP_EMBED: "embed",
-             OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8", OP_RANDN: "randn", OP_TWIN_FOLD: "twin_fold", OP_SCAN: "scan"}
+             OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8", OP_RANDN: "randn", OP_TWIN_FOLD: "twin_fold", OP_SCAN: "scan",
+             OP_RANDN_BATCH: "randn_batch", OP_CANNY_U8_BATCH: "canny_u8_batch"}
 
 EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", "i2i_igemm", "i2i_igemm_gn_parts", "i2i_igemm_route", "i2i_gn_stats",
            "i2i_gn_apply", "i2i_nop", "i2i_calib_mfma", "i2i_calib_stream", "i2i_layernorm", "i2i_softmax", "i2i_attention", "i2i_nchw_to_nhwc",
            "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_canny_ws_bytes", "i2i_randn", "i2i_twin_fold", "i2i_scan",
+           "i2i_randn_batch", "i2i_canny_u8_batch",
            "i2i_merge_group_create", "i2i_merge_group_run", "i2i_merge_group_destroy", "i2i_run", "i2i_run_timed",
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
@@ -204,7 +217,8 @@ class Library:
         L.i2i_last_error.restype = C.c_char_p
         L.i2i_sizeof_op.restype = C.c_size_t
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
-                     "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan"):
+                     "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
+                     "i2i_randn_batch", "i2i_canny_u8_batch"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]

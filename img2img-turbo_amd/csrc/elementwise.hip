@@ -165,15 +165,13 @@ __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, uint32_t& x
     y = __builtin_bit_cast(uint32_t, rad * sinpi_f(t));
 }
 
+// dst[0 .. n) from one state: the body of both noise kernels (a counter per thread, grid-stride along x)
 template <bool NORMAL>
-__global__ __launch_bounds__(256) void randn_kernel(const i2i_randn_params p) {
-    const uint32_t k0 = p.state ? p.state[0] : (uint32_t)p.seed, k1 = p.state ? p.state[1] : (uint32_t)(p.seed >> 32);
-    const uint32_t step = p.state ? p.state[2] : p.step;
-    uint32_t* dst = (uint32_t*)p.dst;
+__device__ __forceinline__ void randn_fill(uint32_t* dst, int64_t n, uint32_t k0, uint32_t k1, uint32_t step, uint32_t stream_id) {
     const bool wide = ((uintptr_t)dst & 15) == 0;          // dst + 4q is then 16-byte aligned for every q
-    const int64_t nq = (p.n + 3) >> 2;
+    const int64_t nq = (n + 3) >> 2;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
-        const u32x4 ctr = {(uint32_t)q, (uint32_t)((uint64_t)q >> 32), step, p.stream_id};
+        const u32x4 ctr = {(uint32_t)q, (uint32_t)((uint64_t)q >> 32), step, stream_id};
         u32x4 w = philox4x32_10(ctr, k0, k1);
         if (NORMAL) {
             uint32_t a, b, c, d;
@@ -183,17 +181,41 @@ __global__ __launch_bounds__(256) void randn_kernel(const i2i_randn_params p) {
             w = g;
         }
         const int64_t i = q << 2;
-        if (wide && i + 4 <= p.n) {
+        if (wide && i + 4 <= n) {
             *(u32x4*)(dst + i) = w;
         } else {
             for (int e = 0; e < 4; ++e)
-                if (i + e < p.n) dst[i + e] = w[e];
+                if (i + e < n) dst[i + e] = w[e];
         }
     }
 }
 
+template <bool NORMAL>
+__global__ __launch_bounds__(256) void randn_kernel(const i2i_randn_params p) {
+    const uint32_t k0 = p.state ? p.state[0] : (uint32_t)p.seed, k1 = p.state ? p.state[1] : (uint32_t)(p.seed >> 32);
+    const uint32_t step = p.state ? p.state[2] : p.step;
+    randn_fill<NORMAL>((uint32_t*)p.dst, p.n, k0, k1, step, p.stream_id);
+}
+
 __global__ __launch_bounds__(64) void randn_advance_kernel(uint32_t* state) {
     if (blockIdx.x == 0 && threadIdx.x == 0) state[2] += 1u;
+}
+
+// per-image states (the contract is the comment of i2i_randn_batch_params): blockIdx.y walks the images, blockIdx.x the counters of one
+// image -- no 64-bit division.  The 16-byte store is decided per image BASE (dst + b * per_image): with per_image % 4 != 0 or a dst
+// that is only 4-byte aligned some bases are misaligned and those images take the element stores; the tail lanes are dropped per image.
+constexpr int RANDN_BATCH_MAX_BLOCKS = 1024;               // workgroups of a fill over all images (4 per CU), as i2i_randn's cap
+
+template <bool NORMAL>
+__global__ __launch_bounds__(256) void randn_batch_kernel(const i2i_randn_batch_params p) {
+    for (int b = (int)blockIdx.y; b < p.batch; b += (int)gridDim.y) {
+        const uint32_t* st = p.states + 4 * (int64_t)b;
+        randn_fill<NORMAL>((uint32_t*)p.dst + (int64_t)b * p.per_image, p.per_image, st[0], st[1], st[2], p.stream_id);
+    }
+}
+
+__global__ __launch_bounds__(256) void randn_batch_advance_kernel(uint32_t* states, int batch) {
+    for (int b = (int)(blockIdx.x * 256 + threadIdx.x); b < batch; b += (int)(gridDim.x * 256)) states[4 * (int64_t)b + 2] += 1u;
 }
 
 // ---- numerical health scan (the contract is the comment of i2i_scan_params).  Everything is done on bit patterns in the element's OWN
@@ -524,6 +546,30 @@ extern "C" int i2i_randn(const i2i_randn_params* p, int /*dtype*/, void* stream)
     if (p->kind == I2I_RANDN_NORMAL) hipLaunchKernelGGL((randn_kernel<true>), dim3(g), dim3(256), 0, s, *p);
     else hipLaunchKernelGGL((randn_kernel<false>), dim3(g), dim3(256), 0, s, *p);
     return i2i::check_launch("randn");
+}
+
+extern "C" int i2i_randn_batch(const i2i_randn_batch_params* p, int /*dtype*/, void* stream) {
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "randn_batch: null params");
+    if (!p->states || ((uintptr_t)p->states & 3)) return i2i::fail(I2I_ERR_BAD_ARG, "randn_batch: states is null or not 4-byte aligned");
+    if (p->batch < 0 || p->per_image < 0) return i2i::fail(I2I_ERR_BAD_ARG, "randn_batch: batch = %d, per_image = %lld", p->batch, (long long)p->per_image);
+    hipStream_t s = (hipStream_t)stream;
+    if (p->kind == I2I_RANDN_ADVANCE) {
+        if (p->batch == 0) return I2I_OK;
+        const int g = (p->batch + 255) / 256;
+        hipLaunchKernelGGL(randn_batch_advance_kernel, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, (uint32_t*)p->states, p->batch);
+        return i2i::check_launch("randn_batch_advance");
+    }
+    if (p->kind != I2I_RANDN_NORMAL && p->kind != I2I_RANDN_RAW) return i2i::fail(I2I_ERR_BAD_ARG, "randn_batch: unknown kind %d", p->kind);
+    if (p->batch == 0 || p->per_image == 0) return I2I_OK;
+    if (p->per_image > ((int64_t)1 << 61) / p->batch) return i2i::fail(I2I_ERR_BAD_ARG, "randn_batch: batch * per_image = %d * %lld is too large", p->batch, (long long)p->per_image);
+    if (!p->dst || ((uintptr_t)p->dst & 3)) return i2i::fail(I2I_ERR_BAD_ARG, "randn_batch: dst is null or not 4-byte aligned");
+    // grid (x, y) = (counters of an image, images), at most RANDN_BATCH_MAX_BLOCKS workgroups in all; both axes are grid-stride loops
+    const unsigned gy = (unsigned)(p->batch > RANDN_BATCH_MAX_BLOCKS ? RANDN_BATCH_MAX_BLOCKS : p->batch);
+    const int64_t b = (((p->per_image + 3) >> 2) + 255) / 256, cap = RANDN_BATCH_MAX_BLOCKS / gy;
+    const unsigned gx = (unsigned)(b > cap ? cap : b);
+    if (p->kind == I2I_RANDN_NORMAL) hipLaunchKernelGGL((randn_batch_kernel<true>), dim3(gx, gy), dim3(256), 0, s, *p);
+    else hipLaunchKernelGGL((randn_batch_kernel<false>), dim3(gx, gy), dim3(256), 0, s, *p);
+    return i2i::check_launch("randn_batch");
 }
 
 extern "C" int i2i_scan(const i2i_scan_params* p, int dtype, void* stream) {

@@ -97,6 +97,8 @@ const std::vector<size_t>& ptr_fields(int opcode) {
                                              PF(twin_fold, bias_pre), PF(twin_fold, w_cur), PF(twin_fold, a_cur), PF(twin_fold, b_cur), PF(twin_fold, bias_cur),
                                              PF(twin_fold, rg)};
     static const std::vector<size_t> scan = {PF(scan, x), PF(scan, rec)};
+    static const std::vector<size_t> randn_batch = {PF(randn_batch, dst), PF(randn_batch, states)};
+    static const std::vector<size_t> canny_batch = {PF(canny_u8_batch, src), PF(canny_u8_batch, dst), PF(canny_u8_batch, thr), PF(canny_u8_batch, ws)};
     switch (opcode) {
         case I2I_OP_IGEMM: return igemm;
         case I2I_OP_GN_STATS: return gn_stats;
@@ -115,6 +117,8 @@ const std::vector<size_t>& ptr_fields(int opcode) {
         case I2I_OP_RANDN: return randn;
         case I2I_OP_TWIN_FOLD: return twin;
         case I2I_OP_SCAN: return scan;
+        case I2I_OP_RANDN_BATCH: return randn_batch;
+        case I2I_OP_CANNY_U8_BATCH: return canny_batch;
         default: return none;
     }
 }

@@ -161,12 +161,15 @@ __device__ __forceinline__ canny_tile canny_tile_of(const i2i_canny_u8_params& p
     return r;
 }
 
-__global__ __launch_bounds__(256) void canny_nms_kernel(const i2i_canny_u8_params p) {
+// thr_stride: int32 words between the {low, high} pairs of consecutive images in p.thr_dev (0 = one pair for the batch: i2i_canny_u8;
+// 2 = i2i_canny_u8_batch).  The only kernel of the five that reads thresholds.
+__global__ __launch_bounds__(256) void canny_nms_kernel(const i2i_canny_u8_params p, const int thr_stride) {
     const int64_t P = (int64_t)p.n * p.h * p.w;
     const canny_ws ws = canny_carve(p.ws, P);
     const canny_tile t = canny_tile_of(p, (int)blockIdx.x);
     const int tid = (int)threadIdx.x;
-    int low = p.thr_dev ? p.thr_dev[0] : p.low, high = p.thr_dev ? p.thr_dev[1] : p.high;
+    const int32_t* thr = p.thr_dev ? p.thr_dev + (int64_t)t.img * thr_stride : nullptr;
+    int low = thr ? thr[0] : p.low, high = thr ? thr[1] : p.high;
     if (low > high) { const int s = low; low = high; high = s; }
 
     uint32_t* pix = (uint32_t*)i2i_smem;                     // [CPH][CPW], channel ch in byte ch
@@ -411,24 +414,43 @@ extern "C" size_t i2i_canny_ws_bytes(int n, int h, int w) {
     return (P * 9 + 15) & ~(size_t)15;
 }
 
-extern "C" int i2i_canny_u8(const i2i_canny_u8_params* p, int dtype, void* stream) {
-    (void)dtype;
-    if (!p || !p->src || !p->dst || !p->ws) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: null pointer");
+// both entries: the checks and the five launches
+static int canny_launch(const char* what, const i2i_canny_u8_params* p, int thr_stride, void* stream) {
+    if (!p->src || !p->dst || !p->ws) return i2i::fail(I2I_ERR_BAD_ARG, "%s: null pointer", what);
     if (p->c < 1 || p->c > 4 || (p->out_c != 1 && p->out_c != 3) || p->n < 1 || p->h < 1 || p->w < 1)
-        return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: bad geometry (c 1..4, out_c 1 or 3, positive sizes)");
+        return i2i::fail(I2I_ERR_BAD_ARG, "%s: bad geometry (c 1..4, out_c 1 or 3, positive sizes)", what);
     const int64_t P = (int64_t)p->n * p->h * p->w;
-    if (P > 0x7fffffff) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: more than 2^31 - 1 pixels in the batch (labels are 32-bit pixel indices)");
-    if (((uintptr_t)p->src | (uintptr_t)p->dst) & 3) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: image batches must be 4-byte aligned");
-    if ((uintptr_t)p->ws & 15) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: the workspace must be 16-byte aligned");
-    if ((uintptr_t)p->thr_dev & 3) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: thr_dev must be 4-byte aligned");
+    if (P > 0x7fffffff) return i2i::fail(I2I_ERR_BAD_ARG, "%s: more than 2^31 - 1 pixels in the batch (labels are 32-bit pixel indices)", what);
+    if (((uintptr_t)p->src | (uintptr_t)p->dst) & 3) return i2i::fail(I2I_ERR_BAD_ARG, "%s: image batches must be 4-byte aligned", what);
+    if ((uintptr_t)p->ws & 15) return i2i::fail(I2I_ERR_BAD_ARG, "%s: the workspace must be 16-byte aligned", what);
+    if ((uintptr_t)p->thr_dev & 3) return i2i::fail(I2I_ERR_BAD_ARG, "%s: thr_dev must be 4-byte aligned", what);
     hipStream_t s = (hipStream_t)stream;
     const int64_t tiles = (int64_t)p->n * ((p->h + CTH - 1) / CTH) * ((p->w + CTW - 1) / CTW);
     auto blocks = [](int64_t total) { const int64_t b = (total + 255) / 256; return (unsigned)(b < 65536 ? b : 65536); };
     const size_t lds_nms = CPH * CPW * 4 + 3 * CMH * CMW * 2, lds_lab = (CMH * CMW + 2) * 4;
-    hipLaunchKernelGGL(canny_nms_kernel, dim3((unsigned)tiles), dim3(256), lds_nms, s, *p);
+    hipLaunchKernelGGL(canny_nms_kernel, dim3((unsigned)tiles), dim3(256), lds_nms, s, *p, thr_stride);
     hipLaunchKernelGGL(canny_label_kernel, dim3((unsigned)tiles), dim3(256), lds_lab, s, *p);
     hipLaunchKernelGGL(canny_merge_kernel, dim3(blocks(P)), dim3(256), 0, s, *p);
     hipLaunchKernelGGL(canny_flag_kernel, dim3(blocks(P)), dim3(256), 0, s, *p);
     hipLaunchKernelGGL(canny_emit_kernel, dim3(blocks((P + 3) / 4)), dim3(256), 0, s, *p);
-    return i2i::check_launch("canny_u8");
+    return i2i::check_launch(what);
+}
+
+extern "C" int i2i_canny_u8(const i2i_canny_u8_params* p, int dtype, void* stream) {
+    (void)dtype;
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8: null pointer");
+    return canny_launch("canny_u8", p, 0, stream);
+}
+
+extern "C" int i2i_canny_u8_batch(const i2i_canny_u8_batch_params* p, int dtype, void* stream) {
+    (void)dtype;
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8_batch: null pointer");
+    if (!p->thr) return i2i::fail(I2I_ERR_BAD_ARG, "canny_u8_batch: thr (device int32 [n][2]) is required");
+    i2i_canny_u8_params q;
+    q.src = p->src; q.dst = p->dst;
+    q.n = p->n; q.h = p->h; q.w = p->w; q.c = p->c; q.out_c = p->out_c;
+    q.low = q.high = 0;
+    q.thr_dev = p->thr;
+    q.ws = p->ws;
+    return canny_launch("canny_u8_batch", &q, 2, stream);
 }

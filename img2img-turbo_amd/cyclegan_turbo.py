@@ -9,7 +9,7 @@ from typing import Optional
 
 import torch
 
-from .pix2pix_turbo import TurboGeneratorBase, _NetHandle
+from .pix2pix_turbo import TurboGeneratorBase, _NetHandle, seed_argument
 from .weights import GeneratorWeights, from_cyclegan_checkpoint, load_checkpoint_file, load_sd_turbo_base
 
 PRETRAINED = {  # src/cyclegan_turbo.py:126-149: name -> (checkpoint file, caption, direction)
@@ -89,9 +89,11 @@ class CycleGAN_Turbo(TurboGeneratorBase):
     @torch.no_grad()
     def forward(self, x_t, direction=None, caption=None, caption_emb=None, *, eps=None, seed=None, _u8_io=None):
         """``seed=s``: the posterior draw comes from the device at (seed s, step 0) under the contract of i2i_randn_params
-        (include/i2i_turbo.h; img2img_turbo_amd.rng) instead of a host-side ``torch.randn``; not together with ``eps=``."""
+        (include/i2i_turbo.h; img2img_turbo_amd.rng) instead of a host-side ``torch.randn``; not together with ``eps=``.
+        ``seed=[s0, .., sB-1]``: one seed per image, slot-independent noise (i2i_randn_batch_params), as Pix2Pix_Turbo.forward."""
         if seed is not None and eps is not None:
             raise ValueError("seed= draws eps on the device: do not pass eps= with it")
+        seed = seed_argument(seed, x_t.shape[0])
         if direction is None:
             assert self.direction is not None
             direction = self.direction
@@ -109,6 +111,7 @@ class CycleGAN_Turbo(TurboGeneratorBase):
             eps = torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
             torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
         ctx_batch = caption_enc.shape[0] if caption_enc.dim() == 3 else 1
-        plan = self.get_plan(B, H, W, direction=direction, ctx_batch=ctx_batch, u8_io=_u8_io, rng=seed is not None)
+        plan = self.get_plan(B, H, W, direction=direction, ctx_batch=ctx_batch, u8_io=_u8_io,
+                             rng=("per_image" if isinstance(seed, list) else seed is not None))
         out = self._execute(plan, x_t, caption_enc, eps, seed=seed)
         return out if _u8_io is not None else out.to(x_t.dtype)

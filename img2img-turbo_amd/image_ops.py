@@ -119,7 +119,9 @@ def canny_u8(images, low=100, high=200, out_channels=3, lib=None):
     """images: uint8 [N, H, W, C] (C <= 4) on the device -> uint8 [N, H, W, out_channels] (1 or 3), 255 on edges: ``cv2.Canny(img, low,
     high)`` (aperture 3, L1 gradient) per image, replicated over the channels as ``canny_from_pil`` does (src/image_prep.py:6-12).  The
     contract is spelled out at i2i_canny_u8_params (include/i2i_turbo.h), tests/canny_ref.py is its CPU oracle; parity with OpenCV itself is
-    unpinned where cv2 is not installed.  Asynchronous on the current stream (five launches in csrc/resize.hip, no read-back)."""
+    unpinned where cv2 is not installed.  Asynchronous on the current stream (five launches in csrc/resize.hip, no read-back).
+    ``low`` / ``high`` may also be sequences of N values, one pair per image (i2i_canny_u8_batch_params: image b of the result is what a
+    call on image b alone with its pair gives, bit for bit); a scalar beside a sequence holds for every image."""
     assert images.dtype == torch.uint8 and images.dim() == 4 and 1 <= images.shape[-1] <= 4
     lib = lib or _capi.default_library()
     n, h, w, c = images.shape
@@ -127,10 +129,24 @@ def canny_u8(images, low=100, high=200, out_channels=3, lib=None):
     dev = src.device
     assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-    lo, hi = canny_thresholds(low, high)
+    per_image = not all(isinstance(v, (int, float)) for v in (low, high))
+    if per_image:
+        lows, highs = [(list(v) if not isinstance(v, (int, float)) else [v] * n) for v in (low, high)]
+        if len(lows) != n or len(highs) != n:
+            raise ValueError("canny_u8: %d low / %d high thresholds for %d images" % (len(lows), len(highs), n))
+        pairs = [canny_thresholds(a, b) for a, b in zip(lows, highs)]
+    else:
+        lo, hi = canny_thresholds(low, high)
     with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
         out = torch.empty((n, h, w, int(out_channels)), dtype=torch.uint8, device=dev)
         ws = torch.empty(max(lib.canny_ws_bytes(n, h, w), 16), dtype=torch.uint8, device=dev)
+        if per_image:
+            thr = torch.tensor(pairs, dtype=torch.int32).reshape(n, 2).to(dev)
+            q = _capi.CannyU8BatchParams()
+            q.src, q.dst, q.ws, q.thr = src.data_ptr(), out.data_ptr(), ws.data_ptr(), thr.data_ptr()
+            q.n, q.h, q.w, q.c, q.out_c = n, h, w, c, int(out_channels)
+            lib.check(lib.lib.i2i_canny_u8_batch(C.addressof(q), 0, stream))
+            return out
         p = _capi.CannyU8Params()
         p.src, p.dst, p.ws, p.thr_dev = src.data_ptr(), out.data_ptr(), ws.data_ptr(), 0
         p.n, p.h, p.w, p.c, p.out_c, p.low, p.high = n, h, w, c, int(out_channels), lo, hi

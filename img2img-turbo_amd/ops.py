@@ -166,6 +166,24 @@ def randn(dst, *, n=None, state=None, seed=0, step=0, stream_id=0, kind=K.RANDN_
     return K.OP_RANDN, _keep(p, dst, state)
 
 
+def randn_batch(dst, states, *, batch, per_image=None, stream_id=0, kind=K.RANDN_NORMAL):
+    """dst[b][0 .. per_image-1] = seeded noise of image b's state row (the contract: i2i_randn_batch_params): ``states`` is the device
+    int32 / uint32 [batch, 4] table read at run time; RANDN_ADVANCE (dst = None) bumps the step word of every row."""
+    p = K.RandnBatchParams()
+    p.dst, p.states, p.batch = ptr(dst), ptr(states), int(batch)
+    p.per_image = ((dst.numel() // max(int(batch), 1)) if dst is not None else 0) if per_image is None else int(per_image)
+    p.stream_id, p.kind = int(stream_id) & 0xFFFFFFFF, int(kind)
+    return K.OP_RANDN_BATCH, _keep(p, dst, states)
+
+
+def canny_u8_batch(src, dst, ws, thr, *, n, h, w, c, out_c=3):
+    """canny_u8 with one {low, high} pair per image: ``thr`` is a device int32 [n, 2] read at run time (i2i_canny_u8_batch_params)."""
+    p = K.CannyU8BatchParams()
+    p.src, p.dst, p.ws, p.thr = ptr(src), ptr(dst), ptr(ws), ptr(thr)
+    p.n, p.h, p.w, p.c, p.out_c = n, h, w, c, out_c
+    return K.OP_CANNY_U8_BATCH, _keep(p, src, dst, ws, thr)
+
+
 def twin_fold(dst, bias, pre, cur, rg, *, bias_pre=None, bias_cur=None):
     """dst[N][K] (+ bias[N]) = the TwinConv fold of two packed layers at the device scale rg[0] (i2i_twin_fold_params).  ``pre`` / ``cur``:
     (w0 fp32 [N][K], A fp32 [rank][K] or None, B fp32 [N][rank] or None)."""

@@ -13,6 +13,7 @@ reference signature and semantics (:186-219).  Differences, all explicit:
 All arithmetic runs in the HIP kernels behind include/i2i_turbo.h; there is no torch/diffusers fallback.
 """
 import collections
+import numbers
 from typing import Optional
 
 import torch
@@ -195,10 +196,14 @@ class TurboGeneratorBase(torch.nn.Module):
         edge detection of "x"; only the boolean is part of the key -- the thresholds are device state of the plan
         (ForwardPlan.set_canny_thresholds), so every (low, high) shares one plan and one captured graph.  ``rng=True``: the program draws
         "eps" (and "noise") itself from the plan's device state (ForwardPlan.set_seed; the contract of i2i_randn_params) and advances the step
-        after every run; again only the boolean is part of the key, every seed shares the plan."""
+        after every run; again only the boolean is part of the key, every seed shares the plan.  ``rng="per_image"`` / ``canny="per_image"``:
+        one noise state / one threshold pair per image of the batch (ForwardPlan.set_seeds, set_canny_thresholds with sequences; the
+        contracts of i2i_randn_batch_params / i2i_canny_u8_batch_params).  The mode is part of the key, so the plans of scalar callers stay
+        theirs."""
         r_plan = float(r) if stochastic else 1.0
         self.set_lora_scale(r_plan)
-        key = ((B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((True,) if canny else ()) + (("rng",) if rng else ())
+        key = ((B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((("canny_per_image",) if canny == "per_image" else (True,)) if canny else ())
+               + ((("rng_per_image",) if rng == "per_image" else ("rng",)) if rng else ())
                + (("health", self.health, self.health_limit) if self.health else ()))
         if key in self._plans:
             self._plans.move_to_end(key)
@@ -207,9 +212,9 @@ class TurboGeneratorBase(torch.nn.Module):
             if u8_io is not None:
                 opts["u8_io"] = u8_io
             if canny:
-                opts["canny"] = True
+                opts["canny"] = canny if canny == "per_image" else True
             if rng:
-                opts["rng"] = True
+                opts["rng"] = rng if rng == "per_image" else True
             if self.health:
                 opts["health"], opts["health_limit"] = self.health, self.health_limit
             with self._on_device():
@@ -256,7 +261,9 @@ class TurboGeneratorBase(torch.nn.Module):
     def _execute(self, plan: ForwardPlan, x, caption_enc, eps, noise_map=None, canny=None, seed=None):
         with self._on_device():
             self.stage(plan, x, caption_enc, eps, noise_map)
-            if seed is not None:
+            if isinstance(seed, list):
+                plan.set_seeds(seed, 0)
+            elif seed is not None:
                 plan.set_seed(seed, 0)
             if canny is not None:
                 plan.set_canny_thresholds(*canny)
@@ -266,6 +273,23 @@ class TurboGeneratorBase(torch.nn.Module):
                 plan.run()
             self._last_plan = plan
             return plan.out.clone()
+
+
+def seed_argument(seed, B):
+    """``seed=`` of the forwards: None, one int (one noise state for the batch), or a sequence of B ints (one per image) -> None | int | list."""
+    if seed is None or isinstance(seed, numbers.Integral):
+        return seed
+    seed = [int(s) for s in seed]
+    if len(seed) != B:
+        raise ValueError("seed= holds %d seeds for a batch of %d (one int, or one per image)" % (len(seed), B))
+    return seed
+
+
+def per_image_mode(canny):
+    """get_plan's canny mode of forward_u8's normalised ``canny``: None -> False, (low, high) -> True, (lows, highs) -> "per_image"."""
+    if canny is None:
+        return False
+    return "per_image" if isinstance(canny[0], list) else True
 
 
 class Pix2Pix_Turbo(TurboGeneratorBase):
@@ -305,13 +329,19 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         cv2.Canny replicated to 3 channels, src/image_prep.py:6-12), after the optional resize and in front of ``to_tensor`` -- the first op
         of the planned program (csrc/resize.hip), so photo -> resize -> Canny -> generator -> uint8 image is one asynchronous sequence.
         Every (low, high) runs the same plan / captured graph (the thresholds are device state).  OpenCV parity is unpinned where cv2 is
-        absent: tests/canny_ref.py is the oracle of the contract in include/i2i_turbo.h.
+        absent: tests/canny_ref.py is the oracle of the contract in include/i2i_turbo.h.  ``canny=[(low, high)] * B``: one pair per image (the
+        requests of a batch keep their own sliders; image b is what a call on image b alone gives, i2i_canny_u8_batch_params).
         ``seed=``: as in ``forward``."""
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
         if canny is not None and canny is not False:
             if sketch:
                 raise ValueError("canny and sketch=True are the two exclusive branches of the script (src/inference_paired.py:47-58)")
-            canny = (100, 200) if canny is True else (canny[0], canny[1])
+            if canny is not True and not isinstance(canny[0], (int, float)):      # a sequence of B pairs -> (lows, highs)
+                if len(canny) != images_u8.shape[0]:
+                    raise ValueError("canny= holds %d (low, high) pairs for a batch of %d" % (len(canny), images_u8.shape[0]))
+                canny = ([p[0] for p in canny], [p[1] for p in canny])
+            else:
+                canny = (100, 200) if canny is True else (canny[0], canny[1])
         else:
             canny = None
         if resize is not None:
@@ -326,9 +356,13 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         """``seed=s``: the scripts' ``torch.manual_seed(s)`` + ``torch.randn`` (src/inference_paired.py:58-60) on the device -- the planned
         program draws "eps" (and, stochastic, the noise map) itself at (seed s, step 0) under the contract of i2i_randn_params
         (include/i2i_turbo.h; img2img_turbo_amd.rng): nothing is staged by the host, the same seed gives the same image on every call, and
-        ``noise_map`` is not needed.  Not together with ``eps=`` / ``noise_map=``.  ``seed=None``: as before."""
+        ``noise_map`` is not needed.  Not together with ``eps=`` / ``noise_map=``.  ``seed=None``: as before.
+        ``seed=[s0, .., sB-1]``: one seed per image, every image at step 0 (the contract of i2i_randn_batch_params): image b's noise is what
+        a batch-1 call with ``seed=sb`` draws, whatever its slot -- the noise, not necessarily every bit of the image (the kernels choose
+        their routes by batch size)."""
         if seed is not None and (eps is not None or noise_map is not None):
             raise ValueError("seed= draws eps and the noise map on the device: do not pass eps= / noise_map= with it")
+        seed = seed_argument(seed, c_t.shape[0])
         if caption_enc is None:
             # either the prompt or the prompt_tokens should be provided (src/pix2pix_turbo.py:188)
             assert (prompt is None) != (prompt_tokens is None), "Either prompt or prompt_tokens should be provided"
@@ -349,8 +383,8 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
             torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
         ctx_batch = caption_enc.shape[0] if caption_enc.dim() == 3 else 1
         assert ctx_batch in (1, B)
-        plan = self.get_plan(B, H, W, stochastic=not deterministic, r=r, ctx_batch=ctx_batch, u8_io=_u8_io, canny=_canny is not None,
-                             rng=seed is not None)
+        plan = self.get_plan(B, H, W, stochastic=not deterministic, r=r, ctx_batch=ctx_batch, u8_io=_u8_io, canny=per_image_mode(_canny),
+                             rng=("per_image" if isinstance(seed, list) else seed is not None))
         out = self._execute(plan, c_t, caption_enc, eps, None if deterministic else noise_map, canny=_canny, seed=seed)
         if _u8_io is not None:
             return out

@@ -164,10 +164,14 @@ class ForwardPlan:
         # canny: the program starts with Canny edge detection of x_in (the edge_to_image script's canny_from_pil, src/inference_paired.py:47-50;
         # csrc/resize.hip): x_in holds the photos, the boundary op reads the plan-owned edge maps.  The thresholds are DEVICE state
         # (canny_thr = {low, high}, read by the kernels at run time), so the program, its hipGraph and an exported plan file follow the
-        # caller's sliders without re-planning.
-        self.canny = bool(canny)
+        # caller's sliders without re-planning.  canny="per_image": one pair per image (canny_thr int32 [B, 2], I2I_OP_CANNY_U8_BATCH) -- the
+        # requests a batching host packed into one replay keep their own sliders.
+        assert canny in (False, True, "per_image"), canny
+        self.canny = canny if canny == "per_image" else bool(canny)
+        self.canny_per_image = canny == "per_image"
         assert not self.canny or u8_io, "canny needs the uint8 boundary (u8_io)"
-        self.canny_thr = torch.tensor([100, 200], dtype=torch.int32, device=device) if self.canny else None
+        self.canny_thr = (torch.tensor([[100, 200]] * B if self.canny_per_image else [100, 200], dtype=torch.int32, device=device)
+                          if self.canny else None)
         self.canny_edges = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if self.canny else None
         self.canny_ws = torch.zeros(max(lib.canny_ws_bytes(B, H, W), 16), dtype=torch.uint8, device=device) if self.canny else None
         self.x_in = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
@@ -177,9 +181,13 @@ class ForwardPlan:
         # rng: the program fills eps (and noise) itself -- seeded noise under the contract of i2i_randn_params (include/i2i_turbo.h), streams 0 and
         # 2 -- from the DEVICE state rng_state = {seed_lo, seed_hi, step, reserved} (uint32 bits in an int32 tensor), and ends by advancing
         # the step: the callers' torch.manual_seed(seed) + torch.randn (src/inference_paired.py:58-60) with one program, one hipGraph and one
-        # plan file for every seed, and fresh noise per replay without the host.
-        self.rng = bool(rng)
-        self.rng_state = torch.zeros(4, dtype=torch.int32, device=device) if self.rng else None
+        # plan file for every seed, and fresh noise per replay without the host.  rng="per_image": one state row per image (rng_state int32
+        # [B, 4], I2I_OP_RANDN_BATCH, the contract of i2i_randn_batch_params): image b's noise is what a batch-1 plan draws at image b's seed and
+        # step, whatever slot the request got -- set with set_seeds.
+        assert rng in (False, True, "per_image"), rng
+        self.rng = rng if rng == "per_image" else bool(rng)
+        self.rng_per_image = rng == "per_image"
+        self.rng_state = torch.zeros((B, 4) if self.rng_per_image else 4, dtype=torch.int32, device=device) if self.rng else None
         self.ctx = torch.zeros(ctx_batch, 77, self.ua.cross_attention_dim, dtype=self.unet_dtype, device=device)
         self.out = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
                     torch.zeros(B, 3, H, W, dtype=self.out_dtype, device=device))
@@ -1072,13 +1080,22 @@ class ForwardPlan:
         self._zero_init = []
         x = self.new(B, H, W, 8)
         mul, add, thr = (tuple(self.u8_io) + (0,))[:3] if self.u8_io else (1.0, 0.0, 0)      # (mul, add[, binarize_below])
-        if self.rng:
+        if self.rng_per_image:
+            from .rng import STREAM_EPS, STREAM_NOISE
+            self._add(O.randn_batch(self.eps, self.rng_state, batch=B, stream_id=STREAM_EPS), "rng.eps", nbytes=self.eps.numel() * 4)
+            if self.noise is not None:
+                self._add(O.randn_batch(self.noise, self.rng_state, batch=B, stream_id=STREAM_NOISE), "rng.noise", nbytes=self.noise.numel() * 4)
+        elif self.rng:
             from .rng import STREAM_EPS, STREAM_NOISE
             self._add(O.randn(self.eps, state=self.rng_state, stream_id=STREAM_EPS), "rng.eps", nbytes=self.eps.numel() * 4)
             if self.noise is not None:
                 self._add(O.randn(self.noise, state=self.rng_state, stream_id=STREAM_NOISE), "rng.noise", nbytes=self.noise.numel() * 4)
         src = self.x_in
-        if self.canny:
+        if self.canny_per_image:
+            self._add(O.canny_u8_batch(self.x_in, self.canny_edges, self.canny_ws, self.canny_thr, n=B, h=H, w=W, c=3, out_c=3), "input.canny",
+                      nbytes=B * H * W * 6)
+            src = self.canny_edges
+        elif self.canny:
             self._add(O.canny_u8(self.x_in, self.canny_edges, self.canny_ws, n=B, h=H, w=W, c=3, out_c=3, thr_dev=self.canny_thr), "input.canny",
                       nbytes=B * H * W * 6)
             src = self.canny_edges
@@ -1109,7 +1126,9 @@ class ForwardPlan:
         self.free(z)
         self._add(O.nhwc_to_nchw(y.t, self.out, n=B, c=3, h=H, w=W, ldx=y.c, clamp=1, mul=0.5, add=0.5), "output.from_nhwc",
                   nbytes=B * H * W * (y.c * self.esz + 3 * self.out.element_size()))
-        if self.rng:          # last: every fill of one run saw the same step
+        if self.rng_per_image:
+            self._add(O.randn_batch(None, self.rng_state, batch=B, kind=K.RANDN_ADVANCE), "rng.advance")
+        elif self.rng:        # last: every fill of one run saw the same step
             self._add(O.randn(None, state=self.rng_state, kind=K.RANDN_ADVANCE), "rng.advance")
         for t in self._zero_init:
             t.zero_()
@@ -1133,9 +1152,19 @@ class ForwardPlan:
     released = False
 
     def set_canny_thresholds(self, low, high):
-        """Write the Canny thresholds the next run / replay uses (floats are floored; asynchronous on the current stream)."""
+        """Write the Canny thresholds the next run / replay uses (floats are floored; asynchronous on the current stream).  On a per-image
+        plan (canny="per_image") ``low`` / ``high`` are scalars (every image) or sequences of B values."""
         assert self.canny, "this plan has no Canny op (get_plan(..., canny=True))"
         from .image_ops import canny_thresholds
+        if self.canny_per_image:
+            lows, highs = [(list(v) if not isinstance(v, (int, float)) else [v] * self.B) for v in (low, high)]
+            if len(lows) != self.B or len(highs) != self.B:
+                raise ValueError("%d low / %d high thresholds for a batch of %d" % (len(lows), len(highs), self.B))
+            for b, pair in enumerate(zip(lows, highs)):
+                lo, hi = canny_thresholds(*pair)
+                self.canny_thr[b, 0:1].fill_(lo)
+                self.canny_thr[b, 1:2].fill_(hi)
+            return
         lo, hi = canny_thresholds(low, high)
         self.canny_thr[0:1].fill_(lo)          # (fill kernels: the values travel as launch arguments, no host buffer to keep alive)
         self.canny_thr[1:2].fill_(hi)
@@ -1144,9 +1173,28 @@ class ForwardPlan:
         """Write the noise state the next run / replay starts from: ``seed`` (reduced mod 2^64) and ``step``.  Every run advances the step
         by one, so set_seed(s) followed by k replays draws steps 0 .. k-1.  Asynchronous on the current stream."""
         assert self.rng, "this plan does not draw its own noise (get_plan(..., rng=True))"
+        assert not self.rng_per_image, "this plan holds one noise state per image (rng=\"per_image\"): use set_seeds(seeds, steps)"
         from .rng import as_i32, pack_state
         for i, word in enumerate(pack_state(seed, step)):
             self.rng_state[i:i + 1].fill_(as_i32(word))          # (fill kernels, as set_canny_thresholds)
+
+    def set_seeds(self, seeds, steps=0):
+        """Per-image plans (rng="per_image"): write the noise state row of every image -- ``seeds``: B ints (each reduced mod 2^64),
+        ``steps``: one int or B ints.  Every run advances every row's step by one.  Asynchronous on the current stream; the values travel as
+        launch arguments of fill kernels, so no host buffer has to outlive the call."""
+        assert self.rng_per_image, "this plan holds one noise state for the batch: use set_seed (or get_plan(..., rng=\"per_image\"))"
+        from .rng import as_i32, pack_states
+        seeds = list(seeds)
+        if len(seeds) != self.B:
+            raise ValueError("%d seeds for a batch of %d" % (len(seeds), self.B))
+        rows = pack_states(seeds, steps)
+        same_step = isinstance(steps, int)          # (the common call: one strided fill for the step column, one for the reserved word)
+        for b, row in enumerate(rows):
+            for i, word in enumerate(row[:2] if same_step else row):
+                self.rng_state[b, i:i + 1].fill_(as_i32(word))
+        if same_step and rows:
+            self.rng_state[:, 2].fill_(as_i32(rows[0][2]))
+            self.rng_state[:, 3].fill_(0)
 
     def _prepare(self):
         if self.released:

@@ -16,7 +16,9 @@ saved with the values of the export, which a host overwrites with i2i_plan_write
 their own noise, --seed N: the 16-byte state {seed_lo, seed_hi, step, reserved} of i2i_randn_params, saved with the exported seed at step 0;
 the program overwrites "eps" / "noise", which a host may read back, and advances the step after every run), and "health" / "health_names"
 (plans built with health=: the n_taps x 8 uint64 records of the scans, saved zeroed and accumulated by every run, and the n_taps labels as
-NUL-terminated bytes -- io names are 24 bytes, so the labels travel as data; examples/health_host.c prints them).
+NUL-terminated bytes -- io names are 24 bytes, so the labels travel as data; examples/health_host.c prints them).  Per-image plans
+(--seeds S0,S1,.. / --canny-per-image LOW HIGH; ForwardPlan(rng="per_image" / canny="per_image")) have "seed" as 16 * B bytes -- one state row
+per image, i2i_randn_batch_params.states, examples/batch_host.c -- and "canny_thr" as 8 * B bytes, one {low, high} pair per image.
 
 This replaces the reference's ``model(...)`` call (src/pix2pix_turbo.py:186-219, src/cyclegan_turbo.py:241-254) for hosts that are not
 Python; the planner itself (route queries, tile choices, buffer recycling) stays in plan.py and runs once, at export.
@@ -202,7 +204,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH]] [--seed N] [--health stages|all] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH]] [--seed N | --seeds S0,S1,..] [--health stages|all] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -223,6 +225,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="the program draws 'eps' (and 'noise') itself: seeded noise under the contract of "
                     "i2i_randn_params (include/i2i_turbo.h).  N is the seed saved in the file (step 0); a host sets another by writing four "
                     "uint32 {seed_lo, seed_hi, step, 0} to the buffer named 'seed'")
+    ap.add_argument("--seeds", default=None, metavar="S0,S1,..", help="--batch comma-separated seeds: as --seed with ONE noise state per image "
+                    "(i2i_randn_batch_params: image b's noise does not depend on its slot); 'seed' is then 16 bytes per image, row b = {seed_lo, "
+                    "seed_hi, step, 0} of image b")
+    ap.add_argument("--canny-per-image", type=float, nargs=2, default=None, metavar=("LOW", "HIGH"), help="as --canny with one {low, high} pair per "
+                    "image: 'canny_thr' is 8 bytes per image, every row saved as LOW HIGH")
     ap.add_argument("--health", default=None, choices=["stages", "all"], help="numerical health scans in the program (ForwardPlan(health=...)): the file "
                     "gets the buffers 'health' (8 uint64 per scanned tensor, accumulated by every run) and 'health_names' (their labels)")
     ap.add_argument("--live-scale", action="store_true", help="also store the scale program (per-layer merges, TwinConv fold, their fp32 masters and "
@@ -235,6 +242,22 @@ def main(argv=None):
     ap.add_argument("--lib", default=None, help="another build of the kernel library (tests: the CPU emulator)")
     a = ap.parse_args(argv)
     dt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[a.dtype]
+    if a.canny is not None and a.canny_per_image is not None:
+        ap.error("--canny and --canny-per-image are exclusive")
+    canny_mode = "per_image" if a.canny_per_image is not None else (a.canny is not None)
+    if a.canny_per_image is not None:
+        a.canny = a.canny_per_image
+    if a.seed is not None and a.seeds is not None:
+        ap.error("--seed and --seeds are exclusive")
+    seeds = None
+    if a.seeds is not None:
+        try:
+            seeds = [int(s, 0) for s in a.seeds.split(",")]
+        except ValueError:
+            ap.error("--seeds takes comma-separated integers")
+        if len(seeds) != a.batch:
+            ap.error("--seeds holds %d values for --batch %d" % (len(seeds), a.batch))
+    rng_mode = "per_image" if seeds is not None else (a.seed is not None)
     if a.canny is not None and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
         ap.error("--canny requires --u8 on a deterministic pix2pix plan (the edge_to_image branch; not with --sketch / --stochastic)")
     H, W = a.size[0], a.size[-1]
@@ -254,7 +277,7 @@ def main(argv=None):
         from .cyclegan_turbo import CycleGAN_Turbo
         model = CycleGAN_Turbo(**kw)
         u8 = (2.0, -1.0) if a.u8 else None          # CycleGAN callers normalise to [-1, 1] (src/inference_unpaired.py:42-44)
-        plan = model.get_plan(a.batch, H, W, direction=a.direction, u8_io=u8, rng=a.seed is not None)
+        plan = model.get_plan(a.batch, H, W, direction=a.direction, u8_io=u8, rng=rng_mode)
     else:
         from .pix2pix_turbo import Pix2Pix_Turbo
         model = Pix2Pix_Turbo(**kw)
@@ -262,10 +285,12 @@ def main(argv=None):
         # `F.to_tensor(img) < 0.5`), which is what Pix2Pix_Turbo.forward_u8(..., sketch=True) feeds -- a stochastic plan is the sketch model
         u8 = ((1.0, 0.0, 128) if (a.sketch or a.stochastic) else (1.0, 0.0)) if a.u8 else None
         gamma = a.gamma if a.gamma is not None else (0.4 if a.stochastic else 1.0)
-        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=a.canny is not None, rng=a.seed is not None)
+        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=canny_mode, rng=rng_mode)
         if a.canny is not None:
             plan.set_canny_thresholds(*a.canny)
-    if a.seed is not None:
+    if seeds is not None:
+        plan.set_seeds(seeds, 0)
+    elif a.seed is not None:
         plan.set_seed(a.seed, 0)
     info = export_plan(plan, a.out, live_scale=a.live_scale)                 # (re-merges the weights at this plan's r first: plan._prepare)
     print("wrote %s: %d ops%s, %d buffers, %.2f GB of weights, %.2f GB of scratch at load; boundary buffers %s"

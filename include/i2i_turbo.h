@@ -56,7 +56,9 @@ typedef enum {
     I2I_OP_CANNY_U8 = 15,
     I2I_OP_RANDN = 16,
     I2I_OP_TWIN_FOLD = 17,
-    I2I_OP_SCAN = 18
+    I2I_OP_SCAN = 18,
+    I2I_OP_RANDN_BATCH = 19,   /* ABI 14 additions (see the note above i2i_randn_batch_params) */
+    I2I_OP_CANNY_U8_BATCH = 20
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -341,6 +343,51 @@ typedef struct {
     int32_t kind;                      /* i2i_randn_kind */
 } i2i_randn_params;
 
+/* ---- ABI 14 additions: per-image request parameters of a batch (I2I_OP_RANDN_BATCH, I2I_OP_CANNY_U8_BATCH).  They are purely additive --
+ * new opcodes, new structs, new exported functions; no existing struct, opcode number or signature changed and sizeof(i2i_op) did not
+ * grow (the union is sized by i2i_igemm_params) -- so I2I_ABI_VERSION stays 14: every program, plan file and host written against 14
+ * runs unchanged.  A library built before the additions is recognised by the missing symbols (i2i_randn_batch, i2i_canny_u8_batch), and
+ * its plan loader refuses the new opcodes as unknown.
+ *
+ * Per-image seeded noise: i2i_randn over a batch with ONE STATE PER IMAGE, so that the noise of a request does not depend on the slot a
+ * batching host put it in, two requests of one batch can carry their own seeds, and a batch sharded over devices does not repeat image 0's
+ * noise on every shard.
+ *   STATES   device uint32 [batch][4], row b = {seed_lo, seed_hi, step, reserved} of image b (the i2i_randn_params state, per image); the
+ *            reserved word is ignored, whatever it holds.  Read at run time: one program / graph / plan file serves every table.
+ *   ELEMENT  j of image b (dst[b * per_image + j]) is element j of i2i_randn with n = per_image and the state states[b]: lane j & 3 of
+ *            Philox4x32-10 with counter {(j >> 2) & 0xffffffff, (j >> 2) >> 32, states[b][2], stream_id} and key {states[b][0],
+ *            states[b][1]}, then (NORMAL) the same Box-Muller.  The same device functions run: row b of the output is BIT-IDENTICAL to a
+ *            batch-1 i2i_randn at image b's seed and step, in any slot, at any batch size.  A tail with per_image % 4 != 0 drops the
+ *            unused lanes PER IMAGE (image b + 1 starts again at counter 0).
+ *   RAW / NORMAL  as i2i_randn (dst uint32 / fp32).
+ *   ADVANCE  states[b][2] += 1 (wrapping) for every b < batch; nothing else is written (words 0, 1, 3 and dst stay).
+ * dst needs 4-byte alignment only; nothing is written outside dst[0 .. batch * per_image).  One launch for the fill, one for the advance; no
+ * allocation, no synchronisation, graph-capturable.  batch == 0 or per_image == 0 is a successful no-op for the fill kinds.
+ * Errors (I2I_ERR_BAD_ARG): null params; states null or not 4-byte aligned; negative batch / per_image (or a product past 2^61); dst null
+ * or not 4-byte aligned (fill kinds); unknown kind.
+ * This fixes the NOISE of an image.  It does not make image b of a batch-8 forward bit-equal to a batch-1 forward of the same request:
+ * the contraction kernels choose routes and tiles by batch size. */
+typedef struct {
+    void* dst;                         /* fp32 (normal) or uint32 (raw) [batch][per_image], contiguous; ignored by advance */
+    int64_t per_image;                 /* elements per image, >= 0 */
+    int32_t batch;                     /* >= 0 */
+    const uint32_t* states;            /* REQUIRED device [batch][4]: {seed_lo, seed_hi, step, reserved} per image; advance writes [b][2] */
+    uint32_t stream_id;
+    int32_t kind;                      /* i2i_randn_kind: NORMAL / RAW / ADVANCE */
+} i2i_randn_batch_params;
+
+/* Per-image Canny thresholds (ABI 14 addition): i2i_canny_u8 with one {low, high} pair per image, read from the device at run time (the
+ * low / high sliders of gradio_canny2image.py, one pair per request of a batch).  Image b uses {thr[2b], thr[2b + 1]}, swapped if
+ * low > high.  Everything else -- the arithmetic, the five launches, the workspace (i2i_canny_ws_bytes), the alignment rules -- is
+ * i2i_canny_u8's: image b of the result is BIT-IDENTICAL to i2i_canny_u8 on image b alone with image b's pair (images never interact:
+ * tiles, labels and unions stay inside an image).  Errors as i2i_canny_u8, plus thr null or not 4-byte aligned. */
+typedef struct {
+    const void* src; void* dst;        /* uint8 [n][h][w][c] -> uint8 [n][h][w][out_c]; 4-byte aligned */
+    int32_t n, h, w, c, out_c;         /* c 1..4; out_c 1 or 3 */
+    const int32_t* thr;                /* REQUIRED device int32 [n][2] = {low, high} per image */
+    void* ws;                          /* >= i2i_canny_ws_bytes(n, h, w) bytes, 16-byte aligned; contents irrelevant before and after */
+} i2i_canny_u8_batch_params;
+
 /* TwinConv fold on the device (ABI v13): the sketch model's conv_in, `conv_in_pretrained(x) * (1 - r) + conv_in_curr(x) * r`
  * (src/pix2pix_turbo.py:16-26), as ONE packed weight tensor written by a kernel, so that a new r costs no host computation and no upload
  * (with i2i_lora_merge / i2i_merge_group_run it makes r a few bytes of device state: Packer.scale_program).  All operands are packed fp32
@@ -414,6 +461,8 @@ typedef struct {
         i2i_randn_params randn;
         i2i_twin_fold_params twin_fold;
         i2i_scan_params scan;
+        i2i_randn_batch_params randn_batch;
+        i2i_canny_u8_batch_params canny_u8_batch;
     } u;
 } i2i_op;
 
@@ -449,6 +498,9 @@ size_t i2i_canny_ws_bytes(int n, int h, int w);                              /* 
 int i2i_randn(const i2i_randn_params* p, int dtype, void* stream);           /* dtype ignored (fp32 / uint32 data); one launch */
 int i2i_twin_fold(const i2i_twin_fold_params* p, int dtype, void* stream);   /* one launch */
 int i2i_scan(const i2i_scan_params* p, int dtype, void* stream);             /* one launch; dtype = element type of x */
+/* ABI 14 additions (per-image request parameters; the version number did not move: see i2i_randn_batch_params) */
+int i2i_randn_batch(const i2i_randn_batch_params* p, int dtype, void* stream);         /* dtype ignored; one launch */
+int i2i_canny_u8_batch(const i2i_canny_u8_batch_params* p, int dtype, void* stream);   /* dtype ignored; five launches */
 
 /* ---- grouped LoRA re-merge (ABI v13): every adapted layer of a network in ONE launch.  `create` checks the n layers as i2i_lora_merge
  * would (an error names the layer index) and uploads them as a device table with an int32 prefix array of tile counts (synchronous: setup,
@@ -485,7 +537,9 @@ int i2i_graph_destroy(void* graph);
  * (src/pix2pix_turbo.py:186-219) is for a Python host, for one fixed (batch, size, dtype, mode).  Names of the pix2pix / CycleGAN plans:
  * "x" (fp32 NCHW images in [-1, 1], or uint8 NHWC with the u8 boundary), "ctx" ([1 | B][77][1024] text states in the plan's dtype),
  * "eps" (fp32 [B][4][H/8][W/8] posterior noise), "noise" (stochastic plans), "out" (images, NCHW in the plan's output dtype or uint8 NHWC);
- * plans exported with a seed also have "seed" (16 bytes: the i2i_randn_params state; the program then fills "eps" / "noise" itself);
+ * plans exported with a seed also have "seed" (16 bytes: the i2i_randn_params state; the program then fills "eps" / "noise" itself;
+ * 16 * B bytes, one state row per image, in a plan exported with per-image seeds: i2i_randn_batch_params.states, examples/batch_host.c);
+ * edge plans have "canny_thr" (8 bytes {low, high}, or 8 * B bytes with per-image thresholds: i2i_canny_u8_batch_params.thr);
  * plans built with health= also have "health" (n_taps x 8 uint64: the i2i_scan_params records in program order, accumulated over the runs;
  * zero them with i2i_plan_write) and "health_names" (the n_taps labels, each NUL-terminated, as bytes): examples/health_host.c.
  * load / write / read are synchronous; run only enqueues (i2i_run); i2i_plan_ops() hands the program to i2i_graph_create(). */
