@@ -23,6 +23,7 @@ OP_TWIN_FOLD = 17
 OP_SCAN = 18
 OP_RANDN_BATCH = 19      # ABI 14 additions: new opcodes / structs / exports only, so the version number did not move (include/i2i_turbo.h)
 OP_CANNY_U8_BATCH = 20
+OP_RESIZE_U8_RAGGED = 21
 RANDN_NORMAL, RANDN_RAW, RANDN_ADVANCE = 0, 1, 2      # i2i_randn_kind
 
 i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -125,6 +126,17 @@ class CannyU8BatchParams(C.Structure):
     _fields_ = [("src", vp), ("dst", vp), ("n", i32), ("h", i32), ("w", i32), ("c", i32), ("out_c", i32), ("thr", vp), ("ws", vp)]
 
 
+class ResizeImage(C.Structure):
+    """One image of a ragged resize pass (i2i_resize_image, 48 bytes, lives in DEVICE memory: image_ops.ragged_descriptors packs it)."""
+    _fields_ = [("src_off", i64), ("dst_off", i64), ("hin", i32), ("win", i32), ("nout", i32), ("ksize", i32),
+                ("bounds_off", i32), ("coeffs_off", i32), ("reserved", i32 * 2)]
+
+
+class ResizeU8RaggedParams(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("src_bytes", i64), ("dst_bytes", i64), ("images", vp), ("tables", vp), ("tables_len", i64),
+                ("n", i32), ("c", i32), ("axis", i32), ("grid_units", i64), ("bad_mask", vp)]
+
+
 class TwinFoldParams(C.Structure):
     _fields_ = [("dst", vp), ("bias", vp), ("w_pre", vp), ("a_pre", vp), ("b_pre", vp), ("bias_pre", vp),
                 ("w_cur", vp), ("a_cur", vp), ("b_cur", vp), ("bias_cur", vp),
@@ -145,7 +157,7 @@ class _OpUnion(C.Union):
                 ("to_nhwc", NchwToNhwcParams), ("to_nchw", NhwcToNchwParams), ("embed", EmbedParams),
                 ("posterior", PosteriorParams), ("ddpm", DdpmParams), ("lora_merge", LoraMergeParams), ("resize_u8", ResizeU8Params),
                 ("nop", NopParams), ("canny_u8", CannyU8Params), ("randn", RandnParams), ("twin_fold", TwinFoldParams), ("scan", ScanParams),
-                ("randn_batch", RandnBatchParams), ("canny_u8_batch", CannyU8BatchParams)]
+                ("randn_batch", RandnBatchParams), ("canny_u8_batch", CannyU8BatchParams), ("resize_u8_ragged", ResizeU8RaggedParams)]
 
 
 class Op(C.Structure):
@@ -156,12 +168,12 @@ _FIELD_OF = {OP_IGEMM: "igemm", OP_GN_STATS: "gn_stats", OP_GN_APPLY: "gn_apply"
              OP_SOFTMAX: "softmax", OP_ATTENTION: "attention", OP_NCHW_TO_NHWC: "to_nhwc",
              OP_NHWC_TO_NCHW: "to_nchw", OP_POSTERIOR: "posterior", OP_DDPM_POSTQUANT: "ddpm", OP_EMBED: "embed",
              OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8", OP_RANDN: "randn", OP_TWIN_FOLD: "twin_fold", OP_SCAN: "scan",
-             OP_RANDN_BATCH: "randn_batch", OP_CANNY_U8_BATCH: "canny_u8_batch"}
+             OP_RANDN_BATCH: "randn_batch", OP_CANNY_U8_BATCH: "canny_u8_batch", OP_RESIZE_U8_RAGGED: "resize_u8_ragged"}
 
 EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", "i2i_igemm", "i2i_igemm_gn_parts", "i2i_igemm_route", "i2i_gn_stats",
            "i2i_gn_apply", "i2i_nop", "i2i_calib_mfma", "i2i_calib_stream", "i2i_layernorm", "i2i_softmax", "i2i_attention", "i2i_nchw_to_nhwc",
            "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_canny_ws_bytes", "i2i_randn", "i2i_twin_fold", "i2i_scan",
-           "i2i_randn_batch", "i2i_canny_u8_batch",
+           "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_lanczos_ksize", "i2i_lanczos_tables",
            "i2i_merge_group_create", "i2i_merge_group_run", "i2i_merge_group_destroy", "i2i_run", "i2i_run_timed",
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
@@ -218,11 +230,15 @@ class Library:
         L.i2i_sizeof_op.restype = C.c_size_t
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
                      "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
-                     "i2i_randn_batch", "i2i_canny_u8_batch"):
+                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.i2i_canny_ws_bytes.restype = C.c_size_t
+        L.i2i_lanczos_ksize.argtypes = [C.c_int, C.c_int]
+        L.i2i_lanczos_ksize.restype = C.c_int
+        L.i2i_lanczos_tables.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int]
+        L.i2i_lanczos_tables.restype = C.c_int
         L.i2i_nop.argtypes = [vp]
         L.i2i_calib_mfma.argtypes = [C.c_int, C.c_int, vp, vp, vp]
         L.i2i_calib_stream.argtypes = [vp, vp, C.c_size_t, vp]
@@ -260,6 +276,19 @@ class Library:
     def canny_ws_bytes(self, n, h, w):
         """Bytes of the workspace i2i_canny_u8 needs for an [n, h, w, c] batch."""
         return int(self.lib.i2i_canny_ws_bytes(int(n), int(h), int(w)))
+
+    def lanczos_tables(self, in_size, out_size, ksize_capacity=None):
+        """The library's own tap tables (i2i_lanczos_tables, host code): (ksize, bounds int32 [out, 2], coeffs int32 [out, capacity]) as numpy
+        arrays -- what a host that is not Python computes; bit-equal to image_ops.lanczos_coeffs."""
+        import numpy as np
+        ksize = int(self.lib.i2i_lanczos_ksize(int(in_size), int(out_size)))
+        self.check(min(ksize, 0))
+        cap = ksize if ksize_capacity is None else int(ksize_capacity)
+        bounds = np.zeros((int(out_size), 2), dtype=np.int32)
+        coeffs = np.zeros((int(out_size), max(cap, 1)), dtype=np.int32)
+        got = int(self.lib.i2i_lanczos_tables(int(in_size), int(out_size), bounds.ctypes.data, coeffs.ctypes.data, cap))
+        self.check(min(got, 0))
+        return got, bounds, coeffs
 
     # ---- programs -------------------------------------------------------------------------------
     def igemm_gn_parts(self, params, dtype_code, groups):

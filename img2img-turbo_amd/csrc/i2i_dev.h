@@ -149,6 +149,13 @@ __device__ __forceinline__ void agent_add_u64(uint64_t* p, uint64_t v) { (void)_
 __device__ __forceinline__ void agent_max_u64(uint64_t* p, uint64_t v) { (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
 
+// a 32-bit flag word (bad_mask of the ragged resize, resize.hip): OR commutes too
+#ifdef I2I_EMU
+__device__ __forceinline__ void agent_or_u32(uint32_t* p, uint32_t v) { *p |= v; }
+#else
+__device__ __forceinline__ void agent_or_u32(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#endif
+
 // ---- arithmetic of the seeded noise op (randn_kernel, elementwise.hip): the high half of a 32 x 32 bit product (v_mul_hi_u32) and the
 // pi-scaled trigonometric functions (exact argument reduction: no fp32 product with pi).  The host has neither: the emulator reduces
 // the argument (in [0, 2)) to a multiple of 1/2 plus |r| <= 1/4 exactly and evaluates in double, well inside the 1 ulp of the device's.

@@ -99,7 +99,10 @@ const std::vector<size_t>& ptr_fields(int opcode) {
     static const std::vector<size_t> scan = {PF(scan, x), PF(scan, rec)};
     static const std::vector<size_t> randn_batch = {PF(randn_batch, dst), PF(randn_batch, states)};
     static const std::vector<size_t> canny_batch = {PF(canny_u8_batch, src), PF(canny_u8_batch, dst), PF(canny_u8_batch, thr), PF(canny_u8_batch, ws)};
+    static const std::vector<size_t> resize_ragged = {PF(resize_u8_ragged, src), PF(resize_u8_ragged, dst), PF(resize_u8_ragged, images),
+                                                      PF(resize_u8_ragged, tables), PF(resize_u8_ragged, bad_mask)};
     switch (opcode) {
+        case I2I_OP_RESIZE_U8_RAGGED: return resize_ragged;
         case I2I_OP_IGEMM: return igemm;
         case I2I_OP_GN_STATS: return gn_stats;
         case I2I_OP_GN_APPLY: return gn_apply;

@@ -7,9 +7,14 @@
 // (img2img_turbo_amd/image_ops.py restates Pillow's precompute_coeffs / normalize_coeffs_8bpc in double precision).
 //   out = clip8((2^21 + sum_t in[first + t] * k[t]) >> 22)
 // Horizontal pass: a thread per output pixel, one 8-byte load per tap; vertical pass: a thread per 4 bytes of the flattened row.
+// i2i_resize_u8_ragged runs the same passes over a batch of images of different sizes (descriptors and tables on the device), and
+// i2i_lanczos_tables restates the host-side table computation for callers that are not Python.
 //
 // Canny (second half of the file): cv::Canny for 8-bit input, aperture 3, L1 gradient, in integer arithmetic (the contract is the
 // comment of i2i_canny_u8_params in include/i2i_turbo.h; the reference runs it on the host: src/image_prep.py:6-12).
+#include <cmath>
+#include <vector>
+
 #include "i2i_dev.h"
 #include "launch.h"
 
@@ -116,6 +121,208 @@ extern "C" int i2i_resize_u8(const i2i_resize_u8_params* p, int dtype, void* str
         else hipLaunchKernelGGL(resize_v_u8_kernel<1>, dim3(blocks((int64_t)p->n * p->nout * rowb)), dim3(256), 0, s, *p);
     }
     return i2i::check_launch("resize_u8");
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Ragged batch (i2i_resize_u8_ragged, the contract is the comment of i2i_resize_u8_ragged_params in include/i2i_turbo.h): the same two
+// passes with everything that differs between images -- extents, arena offsets, tap tables -- read from a device descriptor.  Grid y = image,
+// grid x = a capacity hint; every workgroup first decides whether its image is empty, valid or rejected (the same verdict in every
+// workgroup of that image: it depends on the descriptor, the table and the launch parameters only), then strides over the image's outputs.
+namespace {
+
+constexpr int RAGGED_MAX_X = 1024;                           // workgroups per image at most
+
+// 0 = empty slot, 1 = run, -1 = rejected.  Called by all 256 threads of the workgroup (two barriers); i2i_smem holds one int.
+__device__ int ragged_verdict(const i2i_resize_u8_ragged_params& p, const i2i_resize_image& d) {
+    if (d.hin == 0 || d.win == 0) return 0;
+    bool ok = d.hin > 0 && d.win > 0 && d.nout >= 1 && d.ksize >= 1 && d.src_off >= 0 && d.dst_off >= 0 && ((d.src_off | d.dst_off) & 3) == 0 &&
+              d.src_off <= p.src_bytes && d.dst_off <= p.dst_bytes && d.bounds_off >= 0 && d.coeffs_off >= 0 && d.bounds_off <= p.tables_len &&
+              d.coeffs_off <= p.tables_len;
+    if (ok) {                                                // sizes as quotients: no product can overflow
+        const int64_t spx = (int64_t)d.hin * d.win;
+        const int64_t dpx = p.axis == 1 ? (int64_t)d.hin * d.nout : (int64_t)d.nout * d.win;
+        ok = spx <= (p.src_bytes - d.src_off) / p.c && dpx <= (p.dst_bytes - d.dst_off) / p.c && 2 * (int64_t)d.nout <= p.tables_len - d.bounds_off &&
+             (int64_t)d.nout * d.ksize <= p.tables_len - d.coeffs_off;
+    }
+    int* verdict = (int*)i2i_smem;
+    if (threadIdx.x == 0) *verdict = ok ? 1 : 0;
+    __syncthreads();
+    if (ok) {                                                // every bounds row: the taps it names lie inside the source extent and the weight row
+        const int extent = p.axis == 1 ? d.win : d.hin;
+        const int32_t* __restrict__ b = p.tables + d.bounds_off;
+        bool rows_ok = true;
+        for (int o = (int)threadIdx.x; o < d.nout; o += 256) {
+            const int first = b[2 * o], cnt = b[2 * o + 1];
+            rows_ok = rows_ok && first >= 0 && cnt >= 0 && cnt <= d.ksize && first <= extent - cnt;
+        }
+        if (!rows_ok) *verdict = 0;                          // (every writer stores the same 0)
+    }
+    __syncthreads();
+    const int v = *verdict;
+    __syncthreads();                                         // the word is reused for the workgroup's next image
+    return v ? 1 : -1;
+}
+
+__device__ __forceinline__ void ragged_h_image(const i2i_resize_u8_ragged_params& p, const i2i_resize_image& d) {
+    const int wo = d.nout, c = p.c;
+    const int64_t total = (int64_t)d.hin * wo;
+    const uint8_t* __restrict__ base = (const uint8_t*)p.src;                 // the ARENA: `a` below is an arena offset
+    const int32_t* __restrict__ bounds = p.tables + d.bounds_off;
+    const int32_t* __restrict__ coeffs = p.tables + d.coeffs_off;
+    uint8_t* __restrict__ dst = (uint8_t*)p.dst + d.dst_off;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int xo = (int)(i % wo);
+        const int64_t y = i / wo;
+        const int first = bounds[2 * xo], cnt = bounds[2 * xo + 1];
+        const int32_t* __restrict__ k = coeffs + (int64_t)xo * d.ksize;
+        int64_t a = d.src_off + (y * d.win + first) * c;
+        int32_t acc[4];
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch) acc[ch] = 1 << 21;
+        if (a + (int64_t)cnt * c + 8 <= p.src_bytes) {       // the last window ends at most 8 - c bytes behind the last tap: inside the arena
+            for (int t = 0; t < cnt; ++t) {
+                const uint32_t* q = (const uint32_t*)(base + (a & ~(int64_t)3));
+                const uint64_t v = ((uint64_t)q[0] | ((uint64_t)q[1] << 32)) >> (8 * (int)(a & 3));
+                const int32_t w = k[t];
+#pragma unroll
+                for (int ch = 0; ch < 4; ++ch)
+                    if (ch < c) acc[ch] += (int32_t)((v >> (8 * ch)) & 0xff) * w;
+                a += c;
+            }
+        } else {                                             // the last pixels of the arena: the image's own bytes only
+            for (int t = 0; t < cnt; ++t) {
+                const int32_t w = k[t];
+#pragma unroll
+                for (int ch = 0; ch < 4; ++ch)
+                    if (ch < c) acc[ch] += (int32_t)base[a + ch] * w;
+                a += c;
+            }
+        }
+        uint8_t* o = dst + i * c;
+#pragma unroll
+        for (int ch = 0; ch < 4; ++ch)
+            if (ch < c) o[ch] = clip8(acc[ch]);
+    }
+}
+
+template <int VEC>
+__device__ __forceinline__ void ragged_v_image(const i2i_resize_u8_ragged_params& p, const i2i_resize_image& d) {
+    const int64_t rowb = (int64_t)d.win * p.c, units = rowb / VEC;
+    const int64_t total = (int64_t)d.nout * units;
+    const int32_t* __restrict__ bounds = p.tables + d.bounds_off;
+    const int32_t* __restrict__ coeffs = p.tables + d.coeffs_off;
+    const uint8_t* __restrict__ src = (const uint8_t*)p.src + d.src_off;
+    uint8_t* __restrict__ dst = (uint8_t*)p.dst + d.dst_off;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t u = i % units;
+        const int yo = (int)(i / units);
+        const int first = bounds[2 * yo], cnt = bounds[2 * yo + 1];
+        const int32_t* __restrict__ k = coeffs + (int64_t)yo * d.ksize;
+        const uint8_t* __restrict__ s = src + (int64_t)first * rowb + u * VEC;
+        int32_t acc[VEC];
+#pragma unroll
+        for (int b = 0; b < VEC; ++b) acc[b] = 1 << 21;
+        for (int t = 0; t < cnt; ++t) {
+            const int32_t w = k[t];
+            if constexpr (VEC == 4) {
+                const uint32_t v = *(const uint32_t*)s;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[b] += (int32_t)((v >> (8 * b)) & 0xff) * w;
+            } else {
+                acc[0] += (int32_t)s[0] * w;
+            }
+            s += rowb;
+        }
+        uint8_t* o = dst + (int64_t)yo * rowb + u * VEC;
+        if constexpr (VEC == 4) {
+            *(uint32_t*)o = (uint32_t)clip8(acc[0]) | ((uint32_t)clip8(acc[1]) << 8) | ((uint32_t)clip8(acc[2]) << 16) | ((uint32_t)clip8(acc[3]) << 24);
+        } else {
+            o[0] = clip8(acc[0]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void resize_ragged_u8_kernel(const i2i_resize_u8_ragged_params p) {
+    for (int b = (int)blockIdx.y; b < p.n; b += (int)gridDim.y) {
+        const i2i_resize_image d = p.images[b];
+        const int v = ragged_verdict(p, d);
+        if (v < 0 && p.bad_mask && blockIdx.x == 0 && threadIdx.x == 0) agent_or_u32(p.bad_mask, 1u << (b & 31));
+        if (v <= 0) continue;
+        if (p.axis == 1) ragged_h_image(p, d);
+        else if (((int64_t)d.win * p.c) % 4 == 0) ragged_v_image<4>(p, d);   // rows of whole dwords (the image base is 4-byte aligned)
+        else ragged_v_image<1>(p, d);
+    }
+}
+
+// Pillow's filter (src/libImaging/Resample.c: sinc_filter, lanczos_filter)
+inline double lanczos_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * 3.14159265358979323846;
+    return sin(x) / x;
+}
+inline double lanczos_weight(double x) { return (-3.0 <= x && x < 3.0) ? lanczos_sinc(x) * lanczos_sinc(x / 3) : 0.0; }
+
+}  // namespace
+
+extern "C" int i2i_resize_u8_ragged(const i2i_resize_u8_ragged_params* p, int dtype, void* stream) {
+    (void)dtype;
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: null pointer");
+    if (p->c < 1 || p->c > 4) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: c = %d outside 1..4", p->c);
+    if (p->n < 0) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: n = %d < 0", p->n);
+    if (p->axis != 0 && p->axis != 1) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: axis = %d (1 = horizontal, 0 = vertical)", p->axis);
+    if (p->grid_units < 1) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: grid_units must be >= 1");
+    if (p->src_bytes < 0 || p->dst_bytes < 0 || p->tables_len < 0) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: negative arena / pool size");
+    if (p->n == 0) return I2I_OK;
+    if (!p->src || !p->dst || !p->images || !p->tables) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: null pointer (src, dst, images, tables)");
+    if (((uintptr_t)p->src | (uintptr_t)p->dst | (uintptr_t)p->tables | (uintptr_t)p->bad_mask) & 3)
+        return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: src, dst, tables and bad_mask must be 4-byte aligned");
+    if ((uintptr_t)p->images & 7) return i2i::fail(I2I_ERR_BAD_ARG, "resize_u8_ragged: images must be 8-byte aligned");
+    const int64_t bx = (p->grid_units + 255) / 256;
+    const dim3 grid((unsigned)(bx < RAGGED_MAX_X ? bx : RAGGED_MAX_X), (unsigned)(p->n < 65535 ? p->n : 65535));
+    hipLaunchKernelGGL(resize_ragged_u8_kernel, grid, dim3(256), 16, (hipStream_t)stream, *p);
+    return i2i::check_launch("resize_u8_ragged");
+}
+
+extern "C" int i2i_lanczos_ksize(int in_size, int out_size) {
+    if (in_size < 1 || out_size < 1) return i2i::fail(I2I_ERR_BAD_ARG, "lanczos_ksize: sizes must be >= 1");
+    const double scale = (double)in_size / out_size, support = 3.0 * (scale < 1.0 ? 1.0 : scale);
+    return (int)ceil(support) * 2 + 1;
+}
+
+// precompute_coeffs + normalize_coeffs_8bpc, statement for statement as image_ops.lanczos_coeffs; a fused multiply-add in
+// `center - support + 0.5` or in the weight's argument would move tap windows, so contraction stays off here whatever the flags say
+extern "C" int i2i_lanczos_tables(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity) {
+#pragma clang fp contract(off)
+    if (!bounds || !coeffs) return i2i::fail(I2I_ERR_BAD_ARG, "lanczos_tables: null pointer");
+    const int ksize = i2i_lanczos_ksize(in_size, out_size);
+    if (ksize < 0) return ksize;
+    if (ksize_capacity < ksize) return i2i::fail(I2I_ERR_BAD_ARG, "lanczos_tables: ksize_capacity %d < ksize %d", ksize_capacity, ksize);
+    const double scale = (double)in_size / out_size, filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 3.0 * filterscale, ss = 1.0 / filterscale;
+    std::vector<double> kk((size_t)ksize);
+    for (int xx = 0; xx < out_size; ++xx) {
+        const double center = 0.0 + (xx + 0.5) * scale;
+        int xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + support + 0.5);
+        if (xmax > in_size) xmax = in_size;
+        xmax -= xmin;
+        double ww = 0.0;
+        for (int x = 0; x < xmax; ++x) {
+            const double w = lanczos_weight(((double)(x + xmin) - center + 0.5) * ss);
+            kk[x] = w;
+            ww += w;
+        }
+        int32_t* row = coeffs + (size_t)xx * ksize_capacity;
+        for (int x = 0; x < ksize_capacity; ++x) {
+            double v = x < xmax ? kk[x] : 0.0;
+            if (x < xmax && ww != 0.0) v /= ww;
+            row[x] = v < 0 ? (int32_t)(-0.5 + v * (double)(1 << 22)) : (int32_t)(0.5 + v * (double)(1 << 22));
+        }
+        bounds[2 * xx] = xmin;
+        bounds[2 * xx + 1] = xmax;
+    }
+    return ksize;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

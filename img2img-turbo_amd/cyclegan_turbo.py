@@ -51,7 +51,14 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         ``ToPILImage()(out*0.5+0.5)`` (:53) run inside the boundary kernels.  ``resize=(width, height)`` applies the script's
         ``transforms.Resize(..., LANCZOS)`` (:40-47, e.g. (512, 512) for "resize_512x512") before the generator and
         ``resize_back=True`` its ``output_pil.resize((input width, input height), Image.LANCZOS)`` (:53) after it, both on the
-        device and bit-identical to Pillow (image_ops.lanczos_resize_u8).  ``seed=``: as in ``forward``."""
+        device and bit-identical to Pillow (image_ops.lanczos_resize_u8).  ``seed=``: as in ``forward``.
+        ``images_u8`` may also be a LIST of uint8 [H_b, W_b, 3] tensors of different sizes -- one request each, as the script handles one
+        file each -- with ``resize=(width, height)`` or ``image_prep="resize_512x512"`` / ``"resize_256x256"`` (and their short forms): two
+        launches bring the batch to the model size and, with ``resize_back=True``, two more take every output back to its request's own size
+        (image_ops.lanczos_resize_u8_ragged); the result is then a list, element b bit-identical to the per-image resize.  A list without a
+        common size in front of the generator (no ``resize``, ``image_prep="resized_crop_512"`` / ``"no_resize"``) is a ValueError."""
+        if isinstance(images_u8, (list, tuple)):
+            return self._forward_u8_list(list(images_u8), *args, resize=resize, resize_back=resize_back, image_prep=image_prep, **kw)
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
         in_hw = images_u8.shape[1:3]
         if image_prep is not None:          # the script's build_transform(args.image_prep) (src/inference_unpaired.py:40, default "resize_512x512")
@@ -68,6 +75,24 @@ class CycleGAN_Turbo(TurboGeneratorBase):
             with self._on_device():
                 out = lanczos_resize_u8(out, (in_hw[1], in_hw[0]), self.lib)
         return out
+
+    def _forward_u8_list(self, images, *args, resize, resize_back, image_prep, **kw):
+        """forward_u8 for a list of images of different sizes (see there)."""
+        from .image_ops import lanczos_resize_u8_ragged
+        sizes = {"resize_256": (256, 256), "resize_256x256": (256, 256), "resize_512": (512, 512), "resize_512x512": (512, 512)}
+        if image_prep is not None and image_prep not in sizes:
+            raise ValueError("image_prep %r does not bring a list of images of different sizes to one size (use resize_256[x256] / "
+                             "resize_512[x512] or resize=(width, height))" % (image_prep,))
+        if image_prep is None and (resize is None or isinstance(resize, str)):
+            raise ValueError("a list of images of different sizes needs resize=(width, height) or a resizing image_prep")
+        size = (int(resize[0]), int(resize[1])) if resize is not None else sizes[image_prep]      # (resize after image_prep wins, as for tensors)
+        with self._on_device():
+            batch = lanczos_resize_u8_ragged(images, size, self.lib)
+        out = self.forward(batch, *args, _u8_io=(2.0, -1.0), **kw)
+        if not resize_back:
+            return out
+        with self._on_device():
+            return lanczos_resize_u8_ragged(out, [(int(t.shape[1]), int(t.shape[0])) for t in images], self.lib)
 
     @staticmethod
     @torch.no_grad()

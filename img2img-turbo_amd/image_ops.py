@@ -7,7 +7,8 @@ Pillow, and Canny edge detection, both of which the reference applies on the hos
 
 The tap windows and 22-bit fixed-point weights are computed here in double precision exactly as Pillow's
 ``precompute_coeffs`` / ``normalize_coeffs_8bpc`` do (src/libImaging/Resample.c); the two integer passes run in
-csrc/resize.hip through ``i2i_resize_u8``.  Pure plumbing otherwise: no pixel arithmetic happens in Python.
+csrc/resize.hip through ``i2i_resize_u8``, or, for a batch of images of different sizes, through ``i2i_resize_u8_ragged`` (two launches
+for the whole batch, ``lanczos_resize_u8_ragged``).  Pure plumbing otherwise: no pixel arithmetic happens in Python.
 """
 import ctypes as C
 import functools
@@ -107,6 +108,144 @@ def lanczos_resize_u8(images, size, lib=None):
             lib.check(lib.lib.i2i_resize_u8(C.addressof(p), 0, stream))
             cur = out
     return cur
+
+
+# ---- mixed-size batches: i2i_resize_u8_ragged (include/i2i_turbo.h), two launches for any number of images of any sizes ----
+# one image of one pass as the kernels read it from device memory (i2i_resize_image, 48 bytes)
+RAGGED_IMAGE_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("hin", "<i4"), ("win", "<i4"), ("nout", "<i4"), ("ksize", "<i4"),
+                               ("bounds_off", "<i4"), ("coeffs_off", "<i4"), ("reserved", "<i4", (2,))])
+assert RAGGED_IMAGE_DTYPE.itemsize == 48
+
+RaggedLayout = collections.namedtuple("RaggedLayout", "n c desc tables src_off mid_off dst_off src_bytes mid_bytes dst_bytes units_h units_v")
+
+
+def _align4(n):
+    return (n + 3) & ~3
+
+
+def ragged_layout(in_hw, out_wh, c, tables_of=lanczos_coeffs):
+    """Host-side packing of one ragged resize (no device work): image b goes from ``in_hw[b]`` = (h, w) to ``out_wh[b]`` = (width, height).
+    Three byte arenas -- sources, the horizontal pass's results [h, width, c], the final images [height, width, c] -- hold the images
+    densely at 4-byte aligned offsets in batch order; one int32 pool holds bounds | coeffs of every distinct (in, out) pair once.
+    ``desc`` is RAGGED_IMAGE_DTYPE [2, n]: row 0 the horizontal pass (sources -> mid), row 1 the vertical pass (mid -> final).  An image
+    with h == 0 or w == 0 is an empty slot (hin = 0 in both passes, no bytes in any arena).  ``units_h`` / ``units_v``: the largest output
+    pixel / output dword (or byte) count of an image, the grid_units of the two launches.  ``tables_of(in, out)`` -> (ksize, bounds,
+    coeffs): lanczos_coeffs, or a library's own i2i_lanczos_tables (Library.lanczos_tables)."""
+    n = len(in_hw)
+    assert len(out_wh) == n and 1 <= c <= 4
+    pool, where, pos = [], {}, 0
+    desc = np.zeros((2, n), dtype=RAGGED_IMAGE_DTYPE)
+    offs = np.zeros((3, n + 1), dtype=np.int64)
+    units_h = units_v = 1
+    for b, ((h, w), (ow, oh)) in enumerate(zip(in_hw, out_wh)):
+        h, w, ow, oh = int(h), int(w), int(ow), int(oh)
+        offs[:, b + 1] = offs[:, b]
+        if h == 0 or w == 0:
+            continue
+        assert h > 0 and w > 0 and ow > 0 and oh > 0
+        tab = []
+        for key in ((w, ow), (h, oh)):
+            if key not in where:
+                ksize, bounds, coeffs = tables_of(*key)
+                where[key] = (ksize, pos, pos + bounds.size)
+                pool += [np.ascontiguousarray(bounds, dtype=np.int32).reshape(-1), np.ascontiguousarray(coeffs, dtype=np.int32).reshape(-1)]
+                pos += bounds.size + coeffs.size
+            tab.append(where[key])
+        desc[0, b] = (offs[0, b], offs[1, b], h, w, ow, tab[0][0], tab[0][1], tab[0][2], (0, 0))
+        desc[1, b] = (offs[1, b], offs[2, b], h, ow, oh, tab[1][0], tab[1][1], tab[1][2], (0, 0))
+        offs[:, b + 1] += (_align4(h * w * c), _align4(h * ow * c), _align4(oh * ow * c))
+        units_h = max(units_h, h * ow)
+        units_v = max(units_v, oh * (ow * c // 4 if (ow * c) % 4 == 0 else ow * c))
+    assert pos < 2 ** 31, "the table pool is indexed with int32"
+    tables = np.concatenate(pool) if pool else np.zeros(1, dtype=np.int32)
+    return RaggedLayout(n, c, desc, tables, offs[0, :n].copy(), offs[1, :n].copy(), offs[2, :n].copy(),
+                        int(offs[0, n]), int(offs[1, n]), int(offs[2, n]), units_h, units_v)
+
+
+def ragged_upload(layout, device):
+    """(descriptors as an int64 device tensor [2 * n * 6], the table pool as an int32 device tensor) of a RaggedLayout."""
+    desc = torch.from_numpy(np.ascontiguousarray(layout.desc).view(np.int64).reshape(-1).copy()) if layout.n else torch.zeros(6, dtype=torch.int64)
+    return desc.to(device), torch.from_numpy(layout.tables.copy()).to(device)
+
+
+def ragged_ops(layout, src, mid, dst, desc_dev, tables_dev, bad_mask=None, units=None):
+    """The two ops of a ragged resize, horizontal then vertical, for _capi.Program.add / direct calls: [(opcode, params)] * 2.  ``units``:
+    (units_h, units_v) to size the grids for a capacity other than this layout's own."""
+    from . import ops as O
+    uh, uv = units or (layout.units_h, layout.units_v)
+    return [O.resize_u8_ragged(src, mid, desc_dev, tables_dev, n=layout.n, c=layout.c, axis=1, grid_units=uh, bad_mask=bad_mask),
+            O.resize_u8_ragged(mid, dst, desc_dev, tables_dev, n=layout.n, c=layout.c, axis=0, grid_units=uv, bad_mask=bad_mask, first_image=layout.n)]
+
+
+_RAGGED_POOLS = collections.OrderedDict()    # (sizes in, sizes out, c, library, device) -> (layout, descriptors, tables) on the device
+_RAGGED_POOLS_MAX = 16
+
+
+def _ragged_pool(lib, in_hw, out_wh, c, device):
+    key = (tuple(in_hw), tuple(out_wh), c, lib.path, str(device))
+    if key in _RAGGED_POOLS:
+        _RAGGED_POOLS.move_to_end(key)
+    else:
+        layout = ragged_layout(in_hw, out_wh, c, tables_of=lib.lanczos_tables)
+        _RAGGED_POOLS[key] = (layout,) + ragged_upload(layout, device)
+        while len(_RAGGED_POOLS) > _RAGGED_POOLS_MAX:
+            _RAGGED_POOLS.popitem(last=False)
+    return _RAGGED_POOLS[key]
+
+
+def lanczos_resize_u8_ragged(images, size, lib=None):
+    """LANCZOS resize of a batch whose images differ in size, in TWO launches whatever the batch holds (i2i_resize_u8_ragged; the eager
+    lanczos_resize_u8 is two launches and two allocations per distinct size).
+    ``images``: a list of uint8 HWC tensors [H_b, W_b, C] on one device (same C <= 4), or one stacked uint8 [N, H, W, C].
+    ``size``: one (width, height) for every image -> a stacked uint8 [N, height, width, C]; or a list of N (width, height) -> a list of
+    uint8 [height_b, width_b, C] tensors (views of one arena).  Image b is bit-identical to ``lanczos_resize_u8(images[b][None], size_b)``,
+    hence (C = 1, 3) to ``Image.resize(size_b, Image.LANCZOS)``.  Asynchronous on the current stream; the tap tables come from the
+    library's i2i_lanczos_tables and are cached per set of sizes."""
+    lib = lib or _capi.default_library()
+    stacked_in = torch.is_tensor(images)
+    if stacked_in:
+        assert images.dtype == torch.uint8 and images.dim() == 4 and 1 <= images.shape[-1] <= 4
+        items = list(images.unbind(0))
+    else:
+        items = list(images)
+        assert all(torch.is_tensor(t) and t.dtype == torch.uint8 and t.dim() == 3 for t in items), "a list of uint8 [H, W, C] tensors"
+    n = len(items)
+    one_size = len(size) == 2 and all(isinstance(v, (int, np.integer)) for v in size)
+    out_wh = [(int(size[0]), int(size[1]))] * n if one_size else [(int(s[0]), int(s[1])) for s in size]
+    if len(out_wh) != n:
+        raise ValueError("lanczos_resize_u8_ragged: %d sizes for %d images" % (len(out_wh), n))
+    if n == 0:
+        raise ValueError("lanczos_resize_u8_ragged: no images")
+    c, dev = items[0].shape[-1], items[0].device
+    if not (1 <= c <= 4) or any(t.shape[-1] != c or t.device != dev for t in items):
+        raise ValueError("lanczos_resize_u8_ragged: the images must share the channel count (1..4) and the device")
+    if any(min(t.shape[0], t.shape[1]) < 1 for t in items) or any(min(s) < 1 for s in out_wh):
+        raise ValueError("lanczos_resize_u8_ragged: empty image or target size")
+    assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
+    in_hw = [(int(t.shape[0]), int(t.shape[1])) for t in items]
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        layout, desc_dev, tables_dev = _ragged_pool(lib, in_hw, out_wh, c, dev)
+        nb = in_hw[0][0] * in_hw[0][1] * c
+        if stacked_in and nb % 4 == 0 and images.is_contiguous() and images.data_ptr() % 4 == 0:
+            src = images.view(-1)                                                # already an arena: dense images at 4-byte aligned offsets
+        else:                                                                    # one concatenation, each image padded to a multiple of 4 bytes
+            pad = torch.zeros(3, dtype=torch.uint8, device=dev)
+            parts = []
+            for t, (h, w) in zip(items, in_hw):
+                parts.append(t.reshape(-1))
+                if (h * w * c) % 4:
+                    parts.append(pad[:4 - (h * w * c) % 4])
+            src = torch.cat(parts)
+        mid = torch.empty(max(layout.mid_bytes, 4), dtype=torch.uint8, device=dev)
+        dst = torch.empty(max(layout.dst_bytes, 4), dtype=torch.uint8, device=dev)
+        for _, p in ragged_ops(layout, src, mid, dst, desc_dev, tables_dev):
+            lib.check(lib.lib.i2i_resize_u8_ragged(C.addressof(p), 0, stream))
+    views = [dst[o:o + oh * ow * c].view(oh, ow, c) for o, (ow, oh) in zip(layout.dst_off.tolist(), out_wh)]
+    if not one_size:
+        return views
+    ow, oh = out_wh[0]
+    return dst[:n * oh * ow * c].view(n, oh, ow, c) if (oh * ow * c) % 4 == 0 else torch.stack(views)
 
 
 def canny_thresholds(low, high):

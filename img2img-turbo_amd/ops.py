@@ -184,6 +184,21 @@ def canny_u8_batch(src, dst, ws, thr, *, n, h, w, c, out_c=3):
     return K.OP_CANNY_U8_BATCH, _keep(p, src, dst, ws, thr)
 
 
+def resize_u8_ragged(src, dst, images, tables, *, n, c, axis, grid_units, bad_mask=None, src_bytes=None, dst_bytes=None, tables_len=None,
+                     first_image=0):
+    """One separable LANCZOS pass over a ragged batch (i2i_resize_u8_ragged_params): ``src`` / ``dst`` are uint8 arenas, ``images`` a device
+    tensor holding n 48-byte descriptors from ``first_image`` on (image_ops.ragged_descriptors), ``tables`` the int32 pool of tap tables.  All
+    three are read at run time; ``grid_units`` sizes the grid only."""
+    p = K.ResizeU8RaggedParams()
+    p.src, p.dst, p.tables, p.bad_mask = ptr(src), ptr(dst), ptr(tables), ptr(bad_mask)
+    p.images = ptr(images) + 48 * int(first_image)
+    p.src_bytes = src.numel() * src.element_size() if src_bytes is None else int(src_bytes)
+    p.dst_bytes = dst.numel() * dst.element_size() if dst_bytes is None else int(dst_bytes)
+    p.tables_len = tables.numel() if tables_len is None else int(tables_len)
+    p.n, p.c, p.axis, p.grid_units = int(n), int(c), int(axis), int(grid_units)
+    return K.OP_RESIZE_U8_RAGGED, _keep(p, src, dst, images, tables, bad_mask)
+
+
 def twin_fold(dst, bias, pre, cur, rg, *, bias_pre=None, bias_cur=None):
     """dst[N][K] (+ bias[N]) = the TwinConv fold of two packed layers at the device scale rg[0] (i2i_twin_fold_params).  ``pre`` / ``cur``:
     (w0 fp32 [N][K], A fp32 [rank][K] or None, B fp32 [N][rank] or None)."""

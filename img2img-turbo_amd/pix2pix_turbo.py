@@ -331,7 +331,18 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         Every (low, high) runs the same plan / captured graph (the thresholds are device state).  OpenCV parity is unpinned where cv2 is
         absent: tests/canny_ref.py is the oracle of the contract in include/i2i_turbo.h.  ``canny=[(low, high)] * B``: one pair per image (the
         requests of a batch keep their own sliders; image b is what a call on image b alone gives, i2i_canny_u8_batch_params).
-        ``seed=``: as in ``forward``."""
+        ``seed=``: as in ``forward``.
+        ``images_u8`` may also be a LIST of uint8 [H_b, W_b, 3] tensors of different sizes with ``resize=(width, height)``: the requests of a
+        batch are brought to the model size in two launches (image_ops.lanczos_resize_u8_ragged) and image b of the result is what the
+        stacked, pre-resized batch gives.  A list needs an explicit size: ``resize=None`` / ``"multiple_of_8"`` would leave the images at
+        different sizes in front of the generator (ValueError)."""
+        if isinstance(images_u8, (list, tuple)):
+            if resize is None or isinstance(resize, str):
+                raise ValueError("a list of images of different sizes needs resize=(width, height): resize=%r leaves them at different sizes" % (resize,))
+            from .image_ops import lanczos_resize_u8_ragged
+            with self._on_device():
+                images_u8 = lanczos_resize_u8_ragged(list(images_u8), (int(resize[0]), int(resize[1])), self.lib)
+            resize = None
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
         if canny is not None and canny is not False:
             if sketch:

@@ -58,7 +58,8 @@ typedef enum {
     I2I_OP_TWIN_FOLD = 17,
     I2I_OP_SCAN = 18,
     I2I_OP_RANDN_BATCH = 19,   /* ABI 14 additions (see the note above i2i_randn_batch_params) */
-    I2I_OP_CANNY_U8_BATCH = 20
+    I2I_OP_CANNY_U8_BATCH = 20,
+    I2I_OP_RESIZE_U8_RAGGED = 21   /* ABI 14 addition (see the note above i2i_resize_u8_ragged_params) */
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -437,6 +438,54 @@ typedef struct {
     uint64_t* rec;                     /* the 8 x uint64 record above */
 } i2i_scan_params;
 
+/* ---- ABI 14 addition: mixed-size images in one batch (I2I_OP_RESIZE_U8_RAGGED).  Purely additive like the two above -- one new opcode, two
+ * new structs, three new exported functions; no existing struct, opcode number or signature changed and sizeof(i2i_op) did not grow -- so
+ * I2I_ABI_VERSION stays 14.  A library built before the addition is recognised by the missing symbol (i2i_resize_u8_ragged), and its plan
+ * loader refuses the new opcode as unknown.
+ *
+ * One separable pass of i2i_resize_u8 over a RAGGED batch: every image has its own extents, its own place in a byte arena and its own tap
+ * table, all read from device memory at run time -- the reference's per-request `Resize((512, 512), LANCZOS)` in front of the generator and
+ * `output.resize(input size, LANCZOS)` behind it (src/inference_unpaired.py:40,53) for a batch of requests of different sizes, in two
+ * launches per direction (axis = 1: win -> nout columns, then axis = 0: hin -> nout rows, Pillow's order) instead of two per image.
+ *   IMAGE b  images[b] (48 bytes): the pass's source is dense HWC [hin][win][c] at src + src_off, its result dense HWC at dst + dst_off
+ *            ([hin][nout][c] for axis = 1, [nout][win][c] for axis = 0).  hin == 0 or win == 0 is an EMPTY SLOT: nothing of it is read
+ *            (not even its other fields) and nothing is written.  bounds[nout][2] = (first tap, tap count) at tables + bounds_off,
+ *            coeffs[nout][ksize] at tables + coeffs_off, exactly the arrays i2i_resize_u8 takes (i2i_lanczos_tables below writes them).
+ *   ARITHMETIC  i2i_resize_u8's: out = clip8((2^21 + sum_t in[first + t] * k[t]) >> 22) in int32.  Image b of the result is BIT-IDENTICAL to
+ *            i2i_resize_u8 on image b alone with the same tables, hence (c = 1, c = 3) to Pillow.  An image that changes along one axis
+ *            only still runs both passes: Pillow's same-size table is an exact identity (one tap of weight 2^22 per coordinate).
+ *   GRID     a function of n and grid_units ONLY (grid y = image, min(ceil(grid_units / 256), 1024) workgroups of 256 per image in x, each
+ *            striding over that image's outputs), so a captured graph stays valid when the host rewrites descriptors, tables and pixels in
+ *            place.  grid_units is a capacity hint -- the largest number of output pixels (axis = 1) or output dwords (axis = 0) any image
+ *            of any request will have; results do not depend on it (1 is correct, only slow).
+ *   SAFETY   Nothing is written outside [dst_off, dst_off + output bytes) of any image; nothing is read outside [0, src_bytes) of the source
+ *            arena (the horizontal pass's 8-byte window loads fall back to byte loads at the arena's end) or outside [0, tables_len) of the
+ *            pool.  The vertical pass uses dword or byte access per image (win * c % 4), chosen at run time.  Before touching pixels every
+ *            workgroup checks its image: offsets non-negative and multiples of 4, source and result inside src_bytes / dst_bytes, both
+ *            tables inside tables_len, nout / ksize >= 1, and every bounds row (0 <= first, 0 <= count <= ksize, first + count <= the
+ *            source extent along `axis`).  An image that fails is SKIPPED as a whole (its destination bytes stay as they were) and bit
+ *            (b & 31) is OR-ed into *bad_mask (if given; the owner zeroes it); the other images are unaffected.  A wrong descriptor or
+ *            table entry is a flag, never a fault.  Images must not overlap in dst; src and dst must not overlap.
+ * One launch, no allocation, no synchronisation, no read-back; graph-capturable.  n == 0 is a successful no-op.
+ * Errors (I2I_ERR_BAD_ARG): null params; c outside 1..4; n < 0; axis not 0 / 1; grid_units < 1; negative src_bytes / dst_bytes / tables_len;
+ * (n > 0) src / dst / images / tables null, src / dst / tables / bad_mask not 4-byte aligned, images not 8-byte aligned. */
+typedef struct {                       /* device, one per image, 48 bytes */
+    int64_t src_off, dst_off;          /* byte offsets into the arenas, multiples of 4 */
+    int32_t hin, win;                  /* extent of this pass's source; hin == 0 or win == 0: empty slot */
+    int32_t nout, ksize;               /* output extent along `axis`; taps per output coordinate (row length of coeffs) */
+    int32_t bounds_off, coeffs_off;    /* int32-element offsets into `tables` */
+    int32_t reserved[2];               /* ignored */
+} i2i_resize_image;
+typedef struct {
+    const void* src; void* dst;        /* uint8 arenas, 4-byte aligned */
+    int64_t src_bytes, dst_bytes;      /* arena capacities */
+    const i2i_resize_image* images;    /* device [n] */
+    const int32_t* tables; int64_t tables_len;   /* device int32 pool and its length in elements */
+    int32_t n, c, axis;                /* c 1..4, shared by the batch; axis as i2i_resize_u8 */
+    int64_t grid_units;                /* capacity hint that sizes the grid ONLY (>= 1) */
+    uint32_t* bad_mask;                /* optional device word */
+} i2i_resize_u8_ragged_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -463,6 +512,7 @@ typedef struct {
         i2i_scan_params scan;
         i2i_randn_batch_params randn_batch;
         i2i_canny_u8_batch_params canny_u8_batch;
+        i2i_resize_u8_ragged_params resize_u8_ragged;
     } u;
 } i2i_op;
 
@@ -501,6 +551,15 @@ int i2i_scan(const i2i_scan_params* p, int dtype, void* stream);             /* 
 /* ABI 14 additions (per-image request parameters; the version number did not move: see i2i_randn_batch_params) */
 int i2i_randn_batch(const i2i_randn_batch_params* p, int dtype, void* stream);         /* dtype ignored; one launch */
 int i2i_canny_u8_batch(const i2i_canny_u8_batch_params* p, int dtype, void* stream);   /* dtype ignored; five launches */
+int i2i_resize_u8_ragged(const i2i_resize_u8_ragged_params* p, int dtype, void* stream);   /* dtype ignored; one launch */
+/* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
+ * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
+ * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
+ * i2i_lanczos_tables: bounds[out][2] = (first tap, tap count) and coeffs[out][ksize_capacity] (22-bit fixed-point weights, zero behind the
+ * count; ksize_capacity >= ksize is the row length, i.e. the `ksize` to put into i2i_resize_u8_params / i2i_resize_image).  Returns ksize,
+ * or I2I_ERR_BAD_ARG (null pointer, size < 1, ksize_capacity too small) with nothing written. */
+int i2i_lanczos_ksize(int in_size, int out_size);
+int i2i_lanczos_tables(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity);
 
 /* ---- grouped LoRA re-merge (ABI v13): every adapted layer of a network in ONE launch.  `create` checks the n layers as i2i_lora_merge
  * would (an error names the layer index) and uploads them as a device table with an int32 prefix array of tile counts (synchronous: setup,
