@@ -420,6 +420,150 @@ template <typename T> int scan_launch(const i2i_scan_params& p, hipStream_t s) {
     return i2i::check_launch("scan");
 }
 
+// ---- the scan over the images of a batch, one record per image (the contract is the comment of i2i_scan_batch_params).  The grid is
+// (slices of an image, images); a workgroup works on ONE image at a time: it loops over the images of its y index, and per image over the
+// chunks / edge elements of its x slice, with the classification (scan_chunk / scan_elem) and the reduction of scan_kernel.
+constexpr int SCAN_BATCH_MAX_GRID = 1024;     // workgroups of one launch at most (as SCAN_MAX_GRID): grid y = min(images, this),
+                                              // grid x = min(workgroups one image can use, this / grid y) slices per image
+
+// The views of ALL images (the host sends a contiguous image down as ONE row of rows * cols elements).  The head / body / tail split is
+// not here: images start img_stride elements apart, so each has its own misalignment, and the kernel derives the split from the image's
+// start address.
+struct ScanBatchArgs {
+    const char* x; int32_t images; int64_t rows, cols, ld, img_stride;
+    uint64_t n_elems; uint32_t thr; uint64_t* rec; int64_t rec_words;       // rec_words: uint64 words between two images' records
+};
+
+template <typename T, bool ONE_ROW>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_batch_kernel(const ScanBatchArgs a) {
+    constexpr int ESZ = (int)sizeof(T), EPC = 16 / ESZ;
+    typedef typename std::conditional<ESZ == 4, uint32_t, uint16_t>::type word_t;
+    uint64_t* red = (uint64_t*)i2i_smem;          // [waves][5]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int b = (int)blockIdx.y; b < a.images; b += (int)gridDim.y) {
+        const char* x = a.x + (int64_t)b * a.img_stride * ESZ;
+        // this image's split, as scan_launch makes it for a single view: elements in front of the first 16-byte boundary, chunks, the rest
+        const int64_t mis = (int64_t)(((uintptr_t)x & 15) / ESZ);
+        int64_t head, nb, tail;
+        if (ONE_ROW) {
+            head = mis ? (EPC - mis < a.cols ? EPC - mis : a.cols) : 0;
+            nb = (a.cols - head) / EPC, tail = a.cols - head - nb * EPC;
+        } else if (mis == 0 && a.ld % EPC == 0) {
+            head = 0, nb = a.cols / EPC, tail = a.cols % EPC;                // every row of this image starts on a 16-byte boundary
+        } else {
+            head = 0, nb = 0, tail = a.cols;                                 // element loads throughout
+        }
+        ScanAcc c = {0u, 0u, 0u, 0u, 0u};
+        const int64_t step = (int64_t)gridDim.x * (SCAN_THREADS * SCAN_UNROLL);
+        const int64_t items = a.rows * nb;
+        const char* body = x + head * ESZ;
+        auto chunk_at = [&](int64_t i) -> const u32x4* {
+            if (ONE_ROW) return (const u32x4*)body + i;
+            const int64_t row = i / nb, j = i - row * nb;
+            return (const u32x4*)(body + row * a.ld * ESZ) + j;
+        };
+        int64_t i0 = (int64_t)blockIdx.x * (SCAN_THREADS * SCAN_UNROLL) + threadIdx.x;
+        for (; i0 + (SCAN_UNROLL - 1) * SCAN_THREADS < items; i0 += step) {
+            u32x4 v[SCAN_UNROLL];
+#pragma unroll
+            for (int u = 0; u < SCAN_UNROLL; ++u) v[u] = *chunk_at(i0 + u * SCAN_THREADS);
+            scan_fence(v);
+#pragma unroll
+            for (int u = 0; u < SCAN_UNROLL; ++u) scan_chunk<T>(v[u], a.thr, c);
+        }
+        if (i0 < items) {               // the last, partial round of this lane
+            for (int u = 0; u < SCAN_UNROLL - 1; ++u) {
+                const int64_t i = i0 + u * SCAN_THREADS;
+                if (i < items) scan_chunk<T>(*chunk_at(i), a.thr, c);
+            }
+        }
+        const int64_t edge = head + tail, n_edge = a.rows * edge;
+        for (int64_t i = (int64_t)blockIdx.x * SCAN_THREADS + threadIdx.x; i < n_edge; i += (int64_t)gridDim.x * SCAN_THREADS) {
+            const int64_t row = ONE_ROW ? 0 : i / edge, e = i - row * edge;
+            const int64_t col = e < head ? e : e + nb * EPC;
+            scan_elem<T>(((const word_t*)x)[row * a.ld + col], a.thr, c);
+        }
+        // scan_kernel's reduction, into this image's record
+        uint32_t amax = c.amax;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint32_t o = __shfl_xor(amax, m);
+            amax = o > amax ? o : amax;
+        }
+        uint64_t cnt[4] = {c.nan, c.pinf, c.ninf, c.over};
+        if (wave_any((c.nan | c.pinf | c.ninf | c.over) != 0u)) {
+#pragma unroll
+            for (int f = 0; f < 4; ++f) cnt[f] = wave_sum_u64(cnt[f]);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int f = 0; f < 4; ++f) red[wave * 5 + f] = cnt[f];
+            red[wave * 5 + 4] = amax;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t* rec = a.rec + (int64_t)b * a.rec_words;
+            uint64_t tot[4] = {0, 0, 0, 0}, mx = 0;
+            for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+                for (int f = 0; f < 4; ++f) tot[f] += red[w * 5 + f];
+                mx = red[w * 5 + 4] > mx ? red[w * 5 + 4] : mx;
+            }
+            for (int f = 0; f < 4; ++f)
+                if (tot[f]) agent_add_u64(rec + 1 + f, tot[f]);
+            if (mx) agent_max_u64(rec + 5, (uint64_t)scan_widen<T>((uint32_t)mx));
+            if (blockIdx.x == 0) {                    // exactly one lane of the launch per image
+                agent_add_u64(rec + 0, 1);
+                if (a.n_elems) agent_add_u64(rec + 6, a.n_elems);
+            }
+        }
+        __syncthreads();                              // `red` is free again before the next image of this workgroup fills it
+    }
+}
+
+template <typename T> int scan_batch_launch(const i2i_scan_batch_params& p, hipStream_t s) {
+    constexpr int64_t EPC = 16 / (int64_t)sizeof(T);
+    if ((uintptr_t)p.x % sizeof(T)) return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: x is not aligned to its element type");
+    ScanBatchArgs a;
+    a.x = (const char*)p.x, a.images = p.images, a.img_stride = p.img_stride;
+    a.n_elems = (uint64_t)p.rows * (uint64_t)p.cols;
+    a.thr = scan_threshold<T>(p.limit);
+    a.rec = p.rec, a.rec_words = p.rec_stride / 8;
+    a.rows = p.rows, a.cols = p.cols, a.ld = p.ld;
+    if (p.ld == p.cols || p.rows <= 1) a.cols = (int64_t)a.n_elems, a.rows = 1, a.ld = a.cols;      // contiguous images: one long row each
+    // slices per image: what the chunk loop of one image can use (1024 chunks per workgroup and pass), or the element loop where an image
+    // has no chunks (upper bounds: the split depends on the image); then the cap on the whole grid
+    const int64_t per = SCAN_THREADS * SCAN_UNROLL;
+    const bool chunks = a.rows == 1 || a.ld % EPC == 0;
+    const int64_t work = chunks ? a.rows * ((a.cols + EPC - 1) / EPC) : a.rows * a.cols, want = (work + per - 1) / per;
+    const unsigned gy = (unsigned)(p.images < SCAN_BATCH_MAX_GRID ? p.images : SCAN_BATCH_MAX_GRID);
+    const int64_t cap = SCAN_BATCH_MAX_GRID / gy;
+    const unsigned gx = (unsigned)(want < 1 ? 1 : (want > cap ? cap : want));
+    const size_t smem = (SCAN_THREADS / 64) * 5 * sizeof(uint64_t);
+    if (a.rows == 1) hipLaunchKernelGGL((scan_batch_kernel<T, true>), dim3(gx, gy), dim3(SCAN_THREADS), smem, s, a);
+    else hipLaunchKernelGGL((scan_batch_kernel<T, false>), dim3(gx, gy), dim3(SCAN_THREADS), smem, s, a);
+    return i2i::check_launch("scan_batch");
+}
+
+// i2i_scan_verdict (the contract is the comment of i2i_scan_verdict_params)
+__global__ __launch_bounds__(256) void scan_verdict_clear_kernel(uint64_t* rec, int64_t words) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) rec[i] = 0;
+}
+
+__global__ __launch_bounds__(256) void scan_verdict_judge_kernel(const uint64_t* rec, int taps, int images, uint32_t* verdict) {
+    for (int b = (int)(blockIdx.x * 256 + threadIdx.x); b < images; b += (int)(gridDim.x * 256)) {      // the lane owns row b
+        uint32_t first_bad = 0, first_over = 0;
+        for (int t = taps - 1; t >= 0; --t) {
+            const uint64_t* r = rec + ((int64_t)t * images + b) * 8;
+            if (r[1] | r[2] | r[3]) first_bad = (uint32_t)t + 1u;
+            if (r[4]) first_over = (uint32_t)t + 1u;
+        }
+        uint32_t* v = verdict + 4 * (int64_t)b;
+        v[0] = first_bad, v[1] = first_over;
+        v[2] += 1u;
+        v[3] += first_bad ? 1u : 0u;
+    }
+}
+
 inline unsigned grid_for(int64_t n) {
     const int64_t b = (n + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -584,4 +728,43 @@ extern "C" int i2i_scan(const i2i_scan_params* p, int dtype, void* stream) {
         case I2I_F16: return scan_launch<_Float16>(*p, s);
         default: return i2i::fail(I2I_ERR_BAD_ARG, "scan: dtype %d is not a float type", dtype);
     }
+}
+
+extern "C" int i2i_scan_batch(const i2i_scan_batch_params* p, int dtype, void* stream) {
+    if (!p || !p->x || !p->rec) return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: null pointer");
+    if (p->images < 1) return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: images = %d < 1", p->images);
+    if (!(p->limit > 0.f)) return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: limit must be > 0");      // (a NaN limit fails the comparison too)
+    if (p->rows < 0 || p->cols < 0 || p->ld < p->cols)
+        return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: rows = %lld, cols = %d, ld = %lld", (long long)p->rows, p->cols, (long long)p->ld);
+    const int64_t big = (int64_t)1 << 61;
+    if (p->rows > 0 && p->ld > big / p->rows) return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: rows * ld = %lld * %lld is too large", (long long)p->rows, (long long)p->ld);
+    const int64_t extent = p->rows > 0 ? (p->rows - 1) * p->ld + p->cols : 0;      // elements from an image's first to behind its last
+    if (p->img_stride < extent || p->img_stride > big / p->images)
+        return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: img_stride = %lld (an image spans %lld elements, %d images)", (long long)p->img_stride, (long long)extent, p->images);
+    if ((uintptr_t)p->rec & 63) return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: rec is not 64-byte aligned");
+    if (p->rec_stride < 64 || (p->rec_stride & 63)) return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: rec_stride = %lld is not a multiple of 64 (>= 64)", (long long)p->rec_stride);
+    hipStream_t s = (hipStream_t)stream;
+    switch (dtype) {
+        case I2I_F32: return scan_batch_launch<float>(*p, s);
+        case I2I_BF16: return scan_batch_launch<__bf16>(*p, s);
+        case I2I_F16: return scan_batch_launch<_Float16>(*p, s);
+        default: return i2i::fail(I2I_ERR_BAD_ARG, "scan_batch: dtype %d is not a float type", dtype);
+    }
+}
+
+extern "C" int i2i_scan_verdict(const i2i_scan_verdict_params* p, int /*dtype*/, void* stream) {
+    if (!p || !p->rec) return i2i::fail(I2I_ERR_BAD_ARG, "scan_verdict: null pointer");
+    if ((uintptr_t)p->rec & 7) return i2i::fail(I2I_ERR_BAD_ARG, "scan_verdict: rec is not 8-byte aligned");
+    if (p->taps < 0 || p->images < 1 || (int64_t)p->taps * p->images > ((int64_t)1 << 40))
+        return i2i::fail(I2I_ERR_BAD_ARG, "scan_verdict: taps = %d, images = %d", p->taps, p->images);
+    hipStream_t s = (hipStream_t)stream;
+    if (p->mode == I2I_VERDICT_CLEAR) {
+        const int64_t words = (int64_t)p->taps * p->images * 8;
+        hipLaunchKernelGGL(scan_verdict_clear_kernel, dim3(grid_for(words)), dim3(256), 0, s, p->rec, words);
+        return i2i::check_launch("scan_verdict_clear");
+    }
+    if (p->mode != I2I_VERDICT_JUDGE) return i2i::fail(I2I_ERR_BAD_ARG, "scan_verdict: unknown mode %d", p->mode);
+    if (!p->verdict || ((uintptr_t)p->verdict & 3)) return i2i::fail(I2I_ERR_BAD_ARG, "scan_verdict: verdict is null or not 4-byte aligned");
+    hipLaunchKernelGGL(scan_verdict_judge_kernel, dim3(grid_for(p->images)), dim3(256), 0, s, (const uint64_t*)p->rec, p->taps, p->images, p->verdict);
+    return i2i::check_launch("scan_verdict_judge");
 }

@@ -101,7 +101,11 @@ const std::vector<size_t>& ptr_fields(int opcode) {
     static const std::vector<size_t> canny_batch = {PF(canny_u8_batch, src), PF(canny_u8_batch, dst), PF(canny_u8_batch, thr), PF(canny_u8_batch, ws)};
     static const std::vector<size_t> resize_ragged = {PF(resize_u8_ragged, src), PF(resize_u8_ragged, dst), PF(resize_u8_ragged, images),
                                                       PF(resize_u8_ragged, tables), PF(resize_u8_ragged, bad_mask)};
+    static const std::vector<size_t> scan_batch = {PF(scan_batch, x), PF(scan_batch, rec)};
+    static const std::vector<size_t> scan_verdict = {PF(scan_verdict, rec), PF(scan_verdict, verdict)};
     switch (opcode) {
+        case I2I_OP_SCAN_BATCH: return scan_batch;
+        case I2I_OP_SCAN_VERDICT: return scan_verdict;
         case I2I_OP_RESIZE_U8_RAGGED: return resize_ragged;
         case I2I_OP_IGEMM: return igemm;
         case I2I_OP_GN_STATS: return gn_stats;

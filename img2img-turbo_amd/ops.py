@@ -221,6 +221,26 @@ def scan(x, rec, *, rows, cols, ld=None, limit):
     return K.OP_SCAN, _keep(p, x, rec)
 
 
+def scan_batch(x, rec, *, images, rows, cols, ld=None, img_stride=None, limit, rec_stride=64):
+    """``scan`` with one record per image (i2i_scan_batch_params): image b is the rows x cols view ``img_stride`` elements behind image
+    b - 1 (default: the images follow each other, rows * ld), its record lies ``rec_stride`` bytes behind the previous image's."""
+    p = K.ScanBatchParams()
+    p.x, p.rec = ptr(x), ptr(rec)
+    ld = int(cols if ld is None else ld)
+    p.images, p.rows, p.cols, p.ld, p.limit = int(images), int(rows), int(cols), ld, float(limit)
+    p.img_stride, p.rec_stride = int(int(rows) * ld if img_stride is None else img_stride), int(rec_stride)
+    return K.OP_SCAN_BATCH, _keep(p, x, rec)
+
+
+def scan_verdict(rec, verdict, *, taps, images, mode):
+    """K.VERDICT_CLEAR: zero the [taps][images][8] records; K.VERDICT_JUDGE: fold them into ``verdict`` (int32 tensor holding uint32 bits,
+    [images][4] = first_bad, first_over, runs, bad_runs) -- i2i_scan_verdict_params."""
+    p = K.ScanVerdictParams()
+    p.rec, p.verdict = ptr(rec), ptr(verdict)
+    p.taps, p.images, p.mode = int(taps), int(images), int(mode)
+    return K.OP_SCAN_VERDICT, _keep(p, rec, verdict)
+
+
 def nhwc_to_nchw(x, y, *, n, c, h, w, ldx, clamp=0, mul=0.0, add=0.0):
     """y: NCHW float tensor, or a uint8 HWC image batch [n, h, w, c] (then y = trunc(clamp01(x*mul+add)*255))."""
     p = K.NhwcToNchwParams()

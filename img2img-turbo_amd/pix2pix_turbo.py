@@ -67,7 +67,7 @@ class TurboGeneratorBase(torch.nn.Module):
 
     def __init__(self, weights: GeneratorWeights, device="cuda", dtype=torch.float32, lib=None,
                  tokenizer=None, text_encoder=None, use_graph=True, fuse_gn=True, flash=True, plan_options=None, unet_dtype=None, live_scale=False,
-                 health=None, health_limit=None):
+                 health=None, health_limit=None, health_per_image=False):
         """``dtype``: element type of activations and packed weights (fp32 = the exact-MFMA parity mode).  ``unet_dtype``: another 16-bit
         type for the UNet alone -- ``dtype=torch.bfloat16, unet_dtype=torch.float16`` keeps the VAE (whose real activations overflow fp16)
         in bf16 and gives the UNet, whose error the 1-step scheduler multiplies by 14.6, fp16's three extra mantissa bits.
@@ -78,10 +78,14 @@ class TurboGeneratorBase(torch.nn.Module):
         ``health="stages"`` / ``"all"``: every plan carries numerical health scans (ForwardPlan(health=...), the contract of i2i_scan_params) --
         per-stage NaN / Inf / near-saturation counts accumulated on the device; read them with ``health_report()`` /
         ``health_first_bad()``, zero them with ``health_reset()``.  ``forward`` itself never synchronises for it; off (None) nothing changes.
-        ``health_limit``: the near-saturation threshold (default: half the largest finite value of each scanned tensor's dtype)."""
+        ``health_limit``: the near-saturation threshold (default: half the largest finite value of each scanned tensor's dtype).
+        ``health_per_image=True`` (with ``health=``): one record per tap AND IMAGE and a per-image verdict computed by the program itself
+        (ForwardPlan(health_per_image=True), the contracts of i2i_scan_batch_params / i2i_scan_verdict_params): ``health_verdict()`` says which
+        request of the batch went non-finite and at which tap; the records then describe the most recent run alone."""
         super().__init__()
         assert health in (None, "stages", "all"), health
-        self.health, self.health_limit = health, health_limit
+        assert health or not health_per_image, "health_per_image needs health=\"stages\" or \"all\""
+        self.health, self.health_limit, self.health_per_image = health, health_limit, bool(health_per_image)
         self._last_plan = None
         self.live_scale = bool(live_scale)
         self.unet_dtype_ = unet_dtype
@@ -142,16 +146,24 @@ class TurboGeneratorBase(torch.nn.Module):
             raise _capi.I2IError("no forward has run yet (or its plan was released)")
         return self._last_plan
 
-    def health_report(self):
-        """One dict per scanned tensor of the most recently run plan, in program order (ForwardPlan.health_report; synchronises)."""
-        return self._health_plan().health_report()
+    def health_report(self, image=None):
+        """One dict per scanned tensor of the most recently run plan, in program order (ForwardPlan.health_report; synchronises).  With
+        ``health_per_image``: of image ``image``, or (the default) aggregated over the images."""
+        return self._health_plan().health_report(image=image)
+
+    def health_verdict(self):
+        """``health_per_image`` models: one dict per image of the most recently run plan -- image, first_bad, first_over (tap labels or None,
+        of the most recent run), runs, bad_runs (totals since the last reset); ForwardPlan.health_verdict, synchronises."""
+        if not self.health_per_image:
+            raise _capi.I2IError("per-image health is off: construct the model with health=... and health_per_image=True")
+        return self._health_plan().health_verdict()
 
     def health_first_bad(self):
         """The first tensor, in program order, that held a NaN or an Inf since the last reset, or None (synchronises)."""
         return self._health_plan().health_first_bad()
 
     def health_reset(self):
-        """Zero the records of the most recently run plan (asynchronous on the current stream)."""
+        """Zero the records (and the per-image verdict rows) of the most recently run plan (asynchronous on the current stream)."""
         self._health_plan().health_reset()
 
     # ---- plumbing ----
@@ -204,7 +216,7 @@ class TurboGeneratorBase(torch.nn.Module):
         self.set_lora_scale(r_plan)
         key = ((B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((("canny_per_image",) if canny == "per_image" else (True,)) if canny else ())
                + ((("rng_per_image",) if rng == "per_image" else ("rng",)) if rng else ())
-               + (("health", self.health, self.health_limit) if self.health else ()))
+               + (("health", self.health, self.health_limit) if self.health else ()) + (("health_per_image",) if self.health_per_image else ()))
         if key in self._plans:
             self._plans.move_to_end(key)
         else:
@@ -217,6 +229,8 @@ class TurboGeneratorBase(torch.nn.Module):
                 opts["rng"] = rng if rng == "per_image" else True
             if self.health:
                 opts["health"], opts["health_limit"] = self.health, self.health_limit
+                if self.health_per_image:
+                    opts["health_per_image"] = True
             with self._on_device():
                 self._plans[key] = ForwardPlan(self.lib, self.weights, B, H, W, self.dtype_, self.device_, stochastic=stochastic,
                                                r=self._r, direction=direction, ctx_batch=ctx_batch, fuse_gn=self.fuse_gn,

@@ -45,6 +45,17 @@ class Pool:
         self.all = []
         self.bytes = 0
         self.no_reuse = False
+        self.private = set()       # data_ptr of the buffers of get_private
+
+    def get_private(self, numel, dtype):
+        """A zeroed buffer with ONE tenant for the life of the plan (put() ignores it): for a tensor whose pad elements are zeroed once
+        and only have to stay finite (the pad columns of V^T).  In a recycled buffer another tenant's NaN would land on them, in whatever
+        image it belonged to, and 0 x NaN would carry it into every later run."""
+        t = torch.zeros(numel, dtype=dtype, device=self.device)
+        self.all.append(t)
+        self.bytes += numel * t.element_size()
+        self.private.add(t.data_ptr())
+        return t
 
     def get(self, numel, dtype):
         key = (numel, dtype)
@@ -57,7 +68,7 @@ class Pool:
         return t
 
     def put(self, t):
-        if self.no_reuse:      # debugging aid: keep every intermediate intact after the run
+        if self.no_reuse or t.data_ptr() in self.private:      # (no_reuse: debugging aid, keeps every intermediate intact after the run)
             return
         self.free_lists.setdefault((t.numel(), t.dtype), []).append(t)
 
@@ -75,7 +86,7 @@ class ForwardPlan:
 
     def __init__(self, lib, weights, B, H, W, dtype, device, *, stochastic=False, r=1.0, direction="a2b",
                  ctx_batch=1, fuse_gn=True, flash=True, out_dtype=None, packers=None, debug=False, dma_small=True, fuse_gn_stats=True, subpix=True, halo_min_tiles=160, u8_io=None, fuse_vae_attention=True,
-                 unet_dtype=None, canny=False, rng=False, health=None, health_limit=None):
+                 unet_dtype=None, canny=False, rng=False, health=None, health_limit=None, health_per_image=False):
         assert H % 8 == 0 and W % 8 == 0, "input must be a multiple of 8 (src/inference_paired.py:38-41)"
         # H, W multiples of 8 suffice (src/inference_paired.py:38-41): latent sizes that are not multiples of 8 make the
         # UNet levels odd (70 -> 35 -> 18 -> 9), handled like diffusers' forward_upsample_size path (explicit sizes).
@@ -110,8 +121,16 @@ class ForwardPlan:
         # encoder / UNet / decoder block's output, moments, latents, the eps-prediction, the decoder's input, the tensor in front of the
         # clamp).  A boundary tensor that a convolution has just written is scanned under both labels in "all".  Each scan runs in the dtype
         # of the tensor it reads; record i of `health_rec` (uint64 [n_taps][8]) belongs to health_labels[i], accumulated until health_reset().
+        # health_per_image: the same taps with ONE RECORD PER IMAGE (I2I_OP_SCAN_BATCH, the contract of i2i_scan_batch_params: every tap is
+        # batch-outermost, so image b is rows / B consecutive rows) and a per-image verdict computed on the device (I2I_OP_SCAN_VERDICT):
+        # `health_rec` is uint64 [n_taps][B][8], the program's FIRST op zeroes it and its LAST op folds it into `health_verdict_rows` (uint32
+        # bits [B][4] = first_bad, first_over, runs, bad_runs) -- after any run or replay the records describe that run and the verdict
+        # rows carry the totals since health_reset(), with nothing staged by the host.  Off (the default) the program is what it was.
         assert health in (None, "stages", "all"), health
+        assert health or not health_per_image, "health_per_image needs health=\"stages\" or \"all\""
         self.health, self.health_limit = health, (None if health_limit is None else float(health_limit))
+        self.health_per_image = bool(health_per_image)
+        self.health_verdict_rows = None
         self.health_labels, self.health_taps, self.health_rec = [], [], None      # health_taps[i] = (tensor, rows, cols, ld) of record i
         self._health_ops = []
         self.prog = K.Program()
@@ -191,7 +210,13 @@ class ForwardPlan:
         self.ctx = torch.zeros(ctx_batch, 77, self.ua.cross_attention_dim, dtype=self.unet_dtype, device=device)
         self.out = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
                     torch.zeros(B, 3, H, W, dtype=self.out_dtype, device=device))
+        if self.health_per_image:
+            self._verdict_ops = [O.scan_verdict(None, None, taps=0, images=B, mode=K.VERDICT_CLEAR),
+                                 O.scan_verdict(None, None, taps=0, images=B, mode=K.VERDICT_JUDGE)]
+            self._add(self._verdict_ops[0], "health: clear", kernel="scan_verdict")
         self._build()
+        if self.health_per_image:
+            self._add(self._verdict_ops[1], "health: verdict", kernel="scan_verdict")
         self._finish_gn_scratch()
         self._finish_health()
         self.prog.freeze()
@@ -237,9 +262,13 @@ class ForwardPlan:
     def _scan(self, label, t, rows, cols, ld=None):
         """Record one scan of the rows x cols view of tensor ``t`` (its own dtype); the record pointer is patched in _finish_health."""
         limit = self.health_limit if self.health_limit is not None else self.HEALTH_LIMIT[t.dtype]
-        op = O.scan(t, None, rows=rows, cols=cols, ld=ld, limit=limit)
+        if self.health_per_image:
+            assert rows % self.B == 0, "tap %s is not batch-outermost: %d rows for a batch of %d" % (label, rows, self.B)
+            op = O.scan_batch(t, None, images=self.B, rows=rows // self.B, cols=cols, ld=ld, limit=limit)
+        else:
+            op = O.scan(t, None, rows=rows, cols=cols, ld=ld, limit=limit)
         with self._as(t.dtype):
-            self._add(op, "health: " + label, kernel="scan_kernel", nbytes=rows * cols * t.element_size())
+            self._add(op, "health: " + label, kernel="scan_batch_kernel" if self.health_per_image else "scan_kernel", nbytes=rows * cols * t.element_size())
         self._health_ops.append(op[1])
         self.health_labels.append(label)
         self.health_taps.append((t, rows, cols, cols if ld is None else ld))
@@ -262,28 +291,51 @@ class ForwardPlan:
         if self.health is None:
             return
         n = len(self._health_ops)
-        self._health_i64 = torch.zeros(max(n, 1), 8, dtype=torch.int64, device=self.device)      # (torch fills / copies int64; the kernel sees uint64)
+        per = self.B if self.health_per_image else 1          # records per tap
+        self._health_i64 = torch.zeros(max(n, 1) * per, 8, dtype=torch.int64, device=self.device)      # (torch fills / copies int64; the kernel sees uint64)
         assert self._health_i64.data_ptr() % 64 == 0
-        self.health_rec = self._health_i64.view(torch.uint64)[:n]
+        self.health_rec = self._health_i64.view(torch.uint64)[:n * per]
         for i, p in enumerate(self._health_ops):
-            p.rec = self._health_i64.data_ptr() + 64 * i
+            p.rec = self._health_i64.data_ptr() + 64 * per * i
             p._keep = tuple(p._keep) + (self._health_i64,)
+        if self.health_per_image:                             # tap-major [n][B][8]: tap i's op walks its B records with rec_stride = 64
+            self.health_rec = self.health_rec.view(n, per, 8)
+            self._verdict_i32 = torch.zeros(self.B, 4, dtype=torch.int32, device=self.device)      # (uint32 bits)
+            self.health_verdict_rows = self._verdict_i32
+            for _, p in self._verdict_ops:
+                p.rec, p.verdict, p.taps = self._health_i64.data_ptr(), self._verdict_i32.data_ptr(), n
+                p._keep = (self._health_i64, self._verdict_i32)
         self.health_names = torch.tensor(list(b"".join(l.encode() + b"\0" for l in self.health_labels)) or [0], dtype=torch.uint8, device=self.device)
 
     def health_reset(self):
-        """Zero every record (a fill on the current stream; asynchronous)."""
+        """Zero every record, and on a per-image plan the verdict rows (fills on the current stream; asynchronous)."""
         assert self.health, "this plan has no health scans (ForwardPlan(health=...))"
         with self._on_device():
             self._health_i64.zero_()
+            if self.health_per_image:
+                self._verdict_i32.zero_()
 
-    def health_report(self):
+    def health_report(self, image=None):
         """Synchronise and return one dict per tap, in program order: label, dtype, runs, n_nan, n_pos_inf, n_neg_inf, n_over, max_abs
-        (a float: the largest finite |x|), elements -- accumulated over every run / replay since the last health_reset()."""
+        (a float: the largest finite |x|), elements -- accumulated over every run / replay since the last health_reset().
+        On a per-image plan the records describe the most recent run alone (the program zeroes them first): ``image=b`` gives the taps of
+        image b, the default their aggregate over the images -- counts and elements summed, max_abs the maximum, runs that of one image --
+        which is what a whole-batch plan reports for one run."""
         assert self.health, "this plan has no health scans (ForwardPlan(health=...))"
         import numpy as np
         if torch.device(self.device).type == "cuda":
             torch.cuda.synchronize(self.device)
         rec = self._health_i64.cpu().numpy().view(np.uint64)
+        if self.health_per_image:
+            rec = rec[:len(self.health_labels) * self.B].reshape(len(self.health_labels), self.B, 8)
+            if image is not None:
+                rec = rec[:, range(self.B)[image]]
+            else:
+                agg = rec.sum(axis=1, dtype=np.uint64)
+                agg[:, 0], agg[:, 5] = rec[:, 0, 0], rec[:, :, 5].max(axis=1)
+                rec = agg
+        else:
+            assert image is None, "this plan keeps one record per tap for the whole batch (ForwardPlan(health_per_image=True))"
         out = []
         for i, (label, (t, _r, _c, _ld)) in enumerate(zip(self.health_labels, self.health_taps)):
             r = [int(v) for v in rec[i]]
@@ -291,8 +343,19 @@ class ForwardPlan:
                             max_abs=float(np.array([r[5]], dtype=np.uint32).view(np.float32)[0]), elements=r[6]))
         return out
 
+    def health_verdict(self):
+        """Per-image plans: synchronise and return one dict per image -- image, first_bad / first_over (the label of the first tap, in
+        program order, at which THIS image held a NaN / Inf, resp. a finite value over the limit, in the most recent run; None if none),
+        runs and bad_runs (totals since the last health_reset()).  The rows are computed by the program's last op."""
+        assert self.health_per_image, "this plan has no per-image verdict (ForwardPlan(health=..., health_per_image=True))"
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(self.device)
+        name = lambda v: self.health_labels[v - 1] if v else None
+        return [dict(image=b, first_bad=name(fb), first_over=name(fo), runs=runs, bad_runs=bad)
+                for b, (fb, fo, runs, bad) in enumerate((int(v) & 0xFFFFFFFF for v in row) for row in self._verdict_i32.cpu().tolist())]
+
     def health_first_bad(self):
-        """The first tap, in program order, that saw a NaN or an Inf (its report dict), or None."""
+        """The first tap, in program order, that saw a NaN or an Inf (its report dict; on a per-image plan the aggregate over the images), or None."""
         for d in self.health_report():
             if d["n_nan"] or d["n_pos_inf"] or d["n_neg_inf"]:
                 return d
@@ -712,7 +775,7 @@ class ForwardPlan:
         qk = self.linear(pk.stacked_linear([prefix + ".to_q", prefix + ".to_k"]), xn.t, B * T, C, label=prefix + ".to_qk")
         wv = pk.conv(prefix + ".to_v")
         Tp = (T + 7) // 8 * 8                      # row pitch of V^T / scores / probabilities (T itself when the plane is /8-aligned)
-        vt = self.pool.get(B * C * Tp, self.dtype)
+        vt = self.pool.get(B * C * Tp, self.dtype) if Tp == T else self.pool.get_private(B * C * Tp, self.dtype)
         self._add(O.bgemm(wv["w"], xn.t, vt, M=C, N=T, Kdim=C, lda=C, ldb=C, ldc=Tp, batch=B, heads=1, a_bs=(0, 0),
                           b_bs=(T * C, 0), c_bs=(C * Tp, 0), bias=wv["b"], bias_mode=2), prefix + ".to_v^T", 2 * B * T * C * C)
         self.flops += 2 * B * T * C * C
@@ -864,7 +927,7 @@ class ForwardPlan:
                 ldvt, vt_stride = nt, tk
                 self._add(one, p + ".to_v^T", 2 * vb * tk * C * kv_cin, kernel="gemm_w32_kernel")
             else:
-                vt, vt_stride = self.pool.get(vb * C * ldvt, self.dtype), C * ldvt
+                vt, vt_stride = (self.pool.get(vb * C * ldvt, self.dtype) if ldvt == tk else self.pool.get_private(vb * C * ldvt, self.dtype)), C * ldvt
                 self._add(O.bgemm(wv["w"], kv_src, vt, M=C, N=tk, Kdim=kv_cin, lda=kv_cin, ldb=kv_cin, ldc=ldvt, batch=vb, heads=1,
                                   a_bs=(0, 0), b_bs=(kv_bs, 0), c_bs=(C * ldvt, 0)), p + ".to_v^T", 2 * vb * tk * C * kv_cin)
             self.flops += 2 * vb * tk * C * kv_cin

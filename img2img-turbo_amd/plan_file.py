@@ -19,6 +19,11 @@ the program overwrites "eps" / "noise", which a host may read back, and advances
 NUL-terminated bytes -- io names are 24 bytes, so the labels travel as data; examples/health_host.c prints them).  Per-image plans
 (--seeds S0,S1,.. / --canny-per-image LOW HIGH; ForwardPlan(rng="per_image" / canny="per_image")) have "seed" as 16 * B bytes -- one state row
 per image, i2i_randn_batch_params.states, examples/batch_host.c -- and "canny_thr" as 8 * B bytes, one {low, high} pair per image.
+Plans with per-image health (--health-per-image with --health; ForwardPlan(health_per_image=True)) have "health" as n_taps x B x 8 uint64
+(tap-major, one record per tap and image: i2i_scan_batch_params; the program zeroes them at the start of every run, so they describe the
+most recent run), "health_names" unchanged, and "verdict" (16 * B bytes: one row of four uint32 {first_bad, first_over, runs, bad_runs} per
+image, written by the program's last op, i2i_scan_verdict_params; totals over the runs).  Export zeroes both; examples/batch_health_host.c
+prints one line per request.
 
 This replaces the reference's ``model(...)`` call (src/pix2pix_turbo.py:186-219, src/cyclegan_turbo.py:241-254) for hosts that are not
 Python; the planner itself (route queries, tile choices, buffer recycling) stays in plan.py and runs once, at export.
@@ -90,10 +95,12 @@ def export_plan(plan, path, extra_tensors=(), live_scale=False):
     if getattr(plan, "health", None):       # the records (zeroed in the file: a loaded plan starts counting at 0) and their labels, NUL-separated
         plan.health_reset()
         named["health"], named["health_names"] = plan._health_i64, plan.health_names
+        if getattr(plan, "health_per_image", False):       # (health_reset zeroed the rows too)
+            named["verdict"] = plan._verdict_i32
     gn_scratch = [t for t in (getattr(plan, n, None) for n in ("gn_partial", "gn_ss", "gn_counters")) if t is not None]
     if getattr(plan, "canny", False):
         gn_scratch += [plan.canny_edges, plan.canny_ws]
-    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed", "health", "health_names"), holders=[plan] + list(extra_tensors), device=plan.device,
+    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed", "health", "health_names", "verdict"), holders=[plan] + list(extra_tensors), device=plan.device,
                           scale_prog=scale_program_of(plan) if live_scale else None)
 
 
@@ -204,7 +211,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH]] [--seed N | --seeds S0,S1,..] [--health stages|all] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH]] [--seed N | --seeds S0,S1,..] [--health stages|all [--health-per-image]] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -232,6 +239,9 @@ def main(argv=None):
                     "image: 'canny_thr' is 8 bytes per image, every row saved as LOW HIGH")
     ap.add_argument("--health", default=None, choices=["stages", "all"], help="numerical health scans in the program (ForwardPlan(health=...)): the file "
                     "gets the buffers 'health' (8 uint64 per scanned tensor, accumulated by every run) and 'health_names' (their labels)")
+    ap.add_argument("--health-per-image", action="store_true", help="with --health: one record per scanned tensor AND image ('health' holds "
+                    "taps x batch x 8 uint64, zeroed by the program at the start of every run) and the buffer 'verdict' (16 bytes per image: "
+                    "uint32 {first_bad, first_over, runs, bad_runs}; first_bad = 1 + the index of the first tap at which that image held a NaN / Inf)")
     ap.add_argument("--live-scale", action="store_true", help="also store the scale program (per-layer merges, TwinConv fold, their fp32 masters and "
                     "LoRA factors): a host then moves the LoRA scale / skip gamma with i2i_plan_set_scale() instead of exporting one file per scale")
     ap.add_argument("--device", default="cuda:0")
@@ -261,7 +271,9 @@ def main(argv=None):
     if a.canny is not None and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
         ap.error("--canny requires --u8 on a deterministic pix2pix plan (the edge_to_image branch; not with --sketch / --stochastic)")
     H, W = a.size[0], a.size[-1]
-    kw = dict(device=a.device, dtype=dt, live_scale=a.live_scale, health=a.health)
+    if a.health_per_image and not a.health:
+        ap.error("--health-per-image needs --health stages|all")
+    kw = dict(device=a.device, dtype=dt, live_scale=a.live_scale, health=a.health, health_per_image=a.health_per_image)
     if a.lib:
         kw["lib"] = K.Library(a.lib)
     if a.synthetic:

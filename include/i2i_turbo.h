@@ -59,7 +59,9 @@ typedef enum {
     I2I_OP_SCAN = 18,
     I2I_OP_RANDN_BATCH = 19,   /* ABI 14 additions (see the note above i2i_randn_batch_params) */
     I2I_OP_CANNY_U8_BATCH = 20,
-    I2I_OP_RESIZE_U8_RAGGED = 21   /* ABI 14 addition (see the note above i2i_resize_u8_ragged_params) */
+    I2I_OP_RESIZE_U8_RAGGED = 21,  /* ABI 14 addition (see the note above i2i_resize_u8_ragged_params) */
+    I2I_OP_SCAN_BATCH = 22,        /* ABI 14 additions (see the note above i2i_scan_batch_params) */
+    I2I_OP_SCAN_VERDICT = 23
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -486,6 +488,57 @@ typedef struct {
     uint32_t* bad_mask;                /* optional device word */
 } i2i_resize_u8_ragged_params;
 
+/* ---- ABI 14 addition: per-image health in a batch (I2I_OP_SCAN_BATCH, I2I_OP_SCAN_VERDICT).  Purely additive like the ones above -- two
+ * new opcodes, two new structs, two new exported functions; no existing struct, opcode number or signature changed and sizeof(i2i_op) did
+ * not grow -- so I2I_ABI_VERSION stays 14.  A library built before the addition is recognised by the missing symbols (i2i_scan_batch,
+ * i2i_scan_verdict), and its plan loader refuses the new opcodes as unknown.
+ *
+ * i2i_scan over the images of a batch-outermost tensor, ONE RECORD PER IMAGE, in one launch: "which request of the batch went non-finite"
+ * (nothing in the forward mixes images, so the other requests of the replay are good and the host can say which).
+ *   IMAGE b  the rows x cols view (row pitch ld, in elements) at x + b * img_stride elements; img_stride >= (rows - 1) * ld + cols.  Images
+ *            may start at any element: every image is split into its own unaligned head, 16-byte chunks and tail from ITS start address.
+ *            Nothing outside [0, cols) of a row of an image is read -- not the padding of a row, not the gap between two images.
+ *   RECORD b the 8 x uint64 record of i2i_scan_params at rec + b * rec_stride BYTES (rec 64-byte aligned, rec_stride a multiple of 64, >= 64).
+ *   CONTRACT after one launch on zeroed records, record b equals BIT FOR BIT what i2i_scan writes for image b's view alone (runs = 1,
+ *            elements = rows * cols per image; rows = 0 or cols = 0 counts a run and reads nothing).  The classification is the same device
+ *            code; every update is an integer add or an unsigned max, so the records do not depend on the grid or on which load path an
+ *            image took, and are identical between the CPU emulator and the GPU.
+ * One launch: the grid is (slices of an image) x (images), capped in total; a workgroup works on one image at a time and issues at most one
+ * agent-scope atomic per non-zero field and image.  No allocation, no synchronisation, no read-back; graph-capturable.
+ * Errors (I2I_ERR_BAD_ARG, the records stay untouched): null params / x / rec; images < 1; negative rows / cols; ld < cols; img_stride smaller
+ * than one image's extent (or sizes whose products leave 2^61); limit not > 0 (NaN included); rec not 64-byte aligned; rec_stride < 64 or
+ * not a multiple of 64; x not aligned to its element; a dtype other than the three float types. */
+typedef struct {
+    const void* x;
+    int32_t images;                    /* >= 1 */
+    int32_t cols;
+    int64_t rows, ld;                  /* rows per image; row pitch in elements, >= cols */
+    int64_t img_stride;                /* elements between image starts */
+    float limit;                       /* as i2i_scan_params.limit */
+    uint64_t* rec;                     /* record of image 0 */
+    int64_t rec_stride;                /* BYTES between the records of consecutive images */
+} i2i_scan_batch_params;
+
+/* The per-image verdict over a table of such records, computed on the device.  Records are TAP-MAJOR: record (t, b) = rec[(t * images + b) * 8
+ * .. + 8), t < taps in program order (what a planner gets with rec = table + t * images * 64 and rec_stride = 64 in tap t's
+ * i2i_scan_batch_params).  verdict = images rows of four uint32 {first_bad, first_over, runs, bad_runs}.
+ *   I2I_VERDICT_CLEAR  zeroes every record of the table.  `verdict` is not touched (it may be NULL).
+ *   I2I_VERDICT_JUDGE  one lane per image b:  first_bad = 1 + the smallest t whose record has n_nan | n_pos_inf | n_neg_inf != 0, or 0 if there
+ *                      is none;  first_over = the same for n_over;  runs += 1;  bad_runs += (first_bad != 0).  The records are only read.  A
+ *                      lane owns its row: plain loads and stores, no atomics.
+ * CLEAR as the first op of a program and JUDGE as its last: after any run or graph replay the records describe THAT run in detail and the
+ * verdict rows carry the running totals, with nothing staged by the host in between.  The owner zeroes the verdict rows.
+ * One launch each; no allocation, no synchronisation, no read-back; graph-capturable.  taps == 0 is valid (JUDGE then only counts the run).
+ * Errors (I2I_ERR_BAD_ARG, nothing written): null params / rec; rec not 8-byte aligned; taps < 0 (or taps * images past 2^40); images < 1;
+ * an unknown mode; (JUDGE) verdict null or not 4-byte aligned. */
+typedef enum { I2I_VERDICT_CLEAR = 0, I2I_VERDICT_JUDGE = 1 } i2i_verdict_mode;
+typedef struct {
+    uint64_t* rec;                     /* [taps][images][8] */
+    int32_t taps, images;
+    uint32_t* verdict;                 /* [images][4] = {first_bad, first_over, runs, bad_runs} */
+    int32_t mode;                      /* i2i_verdict_mode */
+} i2i_scan_verdict_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -513,6 +566,8 @@ typedef struct {
         i2i_randn_batch_params randn_batch;
         i2i_canny_u8_batch_params canny_u8_batch;
         i2i_resize_u8_ragged_params resize_u8_ragged;
+        i2i_scan_batch_params scan_batch;
+        i2i_scan_verdict_params scan_verdict;
     } u;
 } i2i_op;
 
@@ -552,6 +607,8 @@ int i2i_scan(const i2i_scan_params* p, int dtype, void* stream);             /* 
 int i2i_randn_batch(const i2i_randn_batch_params* p, int dtype, void* stream);         /* dtype ignored; one launch */
 int i2i_canny_u8_batch(const i2i_canny_u8_batch_params* p, int dtype, void* stream);   /* dtype ignored; five launches */
 int i2i_resize_u8_ragged(const i2i_resize_u8_ragged_params* p, int dtype, void* stream);   /* dtype ignored; one launch */
+int i2i_scan_batch(const i2i_scan_batch_params* p, int dtype, void* stream);           /* one launch; dtype = element type of x */
+int i2i_scan_verdict(const i2i_scan_verdict_params* p, int dtype, void* stream);       /* dtype ignored; one launch */
 /* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
  * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
  * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
@@ -600,7 +657,10 @@ int i2i_graph_destroy(void* graph);
  * 16 * B bytes, one state row per image, in a plan exported with per-image seeds: i2i_randn_batch_params.states, examples/batch_host.c);
  * edge plans have "canny_thr" (8 bytes {low, high}, or 8 * B bytes with per-image thresholds: i2i_canny_u8_batch_params.thr);
  * plans built with health= also have "health" (n_taps x 8 uint64: the i2i_scan_params records in program order, accumulated over the runs;
- * zero them with i2i_plan_write) and "health_names" (the n_taps labels, each NUL-terminated, as bytes): examples/health_host.c.
+ * zero them with i2i_plan_write) and "health_names" (the n_taps labels, each NUL-terminated, as bytes): examples/health_host.c;
+ * plans built with per-image health have "health" as n_taps x B x 8 uint64 (tap-major, one i2i_scan_batch_params record per tap and image,
+ * zeroed by the program itself at the start of every run), "health_names" unchanged, and "verdict" (16 * B bytes: one row of four uint32
+ * {first_bad, first_over, runs, bad_runs} per image, i2i_scan_verdict_params; saved zeroed, totals over the runs): examples/batch_health_host.c.
  * load / write / read are synchronous; run only enqueues (i2i_run); i2i_plan_ops() hands the program to i2i_graph_create(). */
 int i2i_plan_load(const char* path, void** plan_out);
 int i2i_plan_io(void* plan, const char* name, void** dev_ptr, size_t* bytes);       /* device address + size of a named buffer */
