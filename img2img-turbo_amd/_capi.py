@@ -25,6 +25,8 @@ OP_RANDN_BATCH = 19      # ABI 14 additions: new opcodes / structs / exports onl
 OP_CANNY_U8_BATCH = 20
 OP_RESIZE_U8_RAGGED = 21
 OP_SCAN_BATCH, OP_SCAN_VERDICT = 22, 23      # per-image health (i2i_scan_batch_params / i2i_scan_verdict_params)
+OP_CANNY_AUTO_THR = 24                      # automatic per-image Canny thresholds (i2i_canny_auto_thr_params)
+FILTER_LANCZOS, FILTER_BICUBIC = 0, 1       # i2i_resample_filter
 VERDICT_CLEAR, VERDICT_JUDGE = 0, 1         # i2i_verdict_mode
 RANDN_NORMAL, RANDN_RAW, RANDN_ADVANCE = 0, 1, 2      # i2i_randn_kind
 
@@ -158,6 +160,10 @@ class ScanVerdictParams(C.Structure):
     _fields_ = [("rec", vp), ("taps", i32), ("images", i32), ("verdict", vp), ("mode", i32)]
 
 
+class CannyAutoThrParams(C.Structure):
+    _fields_ = [("src", vp), ("n", i32), ("h", i32), ("w", i32), ("c", i32), ("sigma_q16", vp), ("thr", vp), ("median2", vp), ("ws", vp)]
+
+
 class NopParams(C.Structure):
     _fields_ = [("unused", i32)]
 
@@ -169,7 +175,7 @@ class _OpUnion(C.Union):
                 ("posterior", PosteriorParams), ("ddpm", DdpmParams), ("lora_merge", LoraMergeParams), ("resize_u8", ResizeU8Params),
                 ("nop", NopParams), ("canny_u8", CannyU8Params), ("randn", RandnParams), ("twin_fold", TwinFoldParams), ("scan", ScanParams),
                 ("randn_batch", RandnBatchParams), ("canny_u8_batch", CannyU8BatchParams), ("resize_u8_ragged", ResizeU8RaggedParams),
-                ("scan_batch", ScanBatchParams), ("scan_verdict", ScanVerdictParams)]
+                ("scan_batch", ScanBatchParams), ("scan_verdict", ScanVerdictParams), ("canny_auto_thr", CannyAutoThrParams)]
 
 
 class Op(C.Structure):
@@ -181,12 +187,13 @@ _FIELD_OF = {OP_IGEMM: "igemm", OP_GN_STATS: "gn_stats", OP_GN_APPLY: "gn_apply"
              OP_NHWC_TO_NCHW: "to_nchw", OP_POSTERIOR: "posterior", OP_DDPM_POSTQUANT: "ddpm", OP_EMBED: "embed",
              OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8", OP_RANDN: "randn", OP_TWIN_FOLD: "twin_fold", OP_SCAN: "scan",
              OP_RANDN_BATCH: "randn_batch", OP_CANNY_U8_BATCH: "canny_u8_batch", OP_RESIZE_U8_RAGGED: "resize_u8_ragged",
-             OP_SCAN_BATCH: "scan_batch", OP_SCAN_VERDICT: "scan_verdict"}
+             OP_SCAN_BATCH: "scan_batch", OP_SCAN_VERDICT: "scan_verdict", OP_CANNY_AUTO_THR: "canny_auto_thr"}
 
 EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", "i2i_igemm", "i2i_igemm_gn_parts", "i2i_igemm_route", "i2i_gn_stats",
            "i2i_gn_apply", "i2i_nop", "i2i_calib_mfma", "i2i_calib_stream", "i2i_layernorm", "i2i_softmax", "i2i_attention", "i2i_nchw_to_nhwc",
            "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_canny_ws_bytes", "i2i_randn", "i2i_twin_fold", "i2i_scan",
            "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_lanczos_ksize", "i2i_lanczos_tables",
+           "i2i_canny_auto_thr", "i2i_canny_auto_ws_bytes", "i2i_resample_ksize", "i2i_resample_tables",
            "i2i_merge_group_create", "i2i_merge_group_run", "i2i_merge_group_destroy", "i2i_run", "i2i_run_timed",
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
@@ -243,11 +250,17 @@ class Library:
         L.i2i_sizeof_op.restype = C.c_size_t
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
                      "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
-                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict"):
+                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.i2i_canny_ws_bytes.restype = C.c_size_t
+        L.i2i_canny_auto_ws_bytes.argtypes = [C.c_int]
+        L.i2i_canny_auto_ws_bytes.restype = C.c_size_t
+        L.i2i_resample_ksize.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.i2i_resample_ksize.restype = C.c_int
+        L.i2i_resample_tables.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
+        L.i2i_resample_tables.restype = C.c_int
         L.i2i_lanczos_ksize.argtypes = [C.c_int, C.c_int]
         L.i2i_lanczos_ksize.restype = C.c_int
         L.i2i_lanczos_tables.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int]
@@ -289,6 +302,24 @@ class Library:
     def canny_ws_bytes(self, n, h, w):
         """Bytes of the workspace i2i_canny_u8 needs for an [n, h, w, c] batch."""
         return int(self.lib.i2i_canny_ws_bytes(int(n), int(h), int(w)))
+
+    def canny_auto_ws_bytes(self, n):
+        """Bytes of the workspace i2i_canny_auto_thr needs for n images (one 256-bin histogram each)."""
+        return int(self.lib.i2i_canny_auto_ws_bytes(int(n)))
+
+    def resample_tables(self, filter, in_size, out_size, ksize_capacity=None):
+        """lanczos_tables for any of the library's filters: ``filter`` = "lanczos" / "bicubic" or an i2i_resample_filter code
+        (i2i_resample_tables, host code); bit-equal to image_ops.resample_coeffs."""
+        import numpy as np
+        code = {"lanczos": FILTER_LANCZOS, "bicubic": FILTER_BICUBIC}.get(filter, filter)
+        ksize = int(self.lib.i2i_resample_ksize(int(code), int(in_size), int(out_size)))
+        self.check(min(ksize, 0))
+        cap = ksize if ksize_capacity is None else int(ksize_capacity)
+        bounds = np.zeros((int(out_size), 2), dtype=np.int32)
+        coeffs = np.zeros((int(out_size), max(cap, 1)), dtype=np.int32)
+        got = int(self.lib.i2i_resample_tables(int(code), int(in_size), int(out_size), bounds.ctypes.data, coeffs.ctypes.data, cap))
+        self.check(min(got, 0))
+        return got, bounds, coeffs
 
     def lanczos_tables(self, in_size, out_size, ksize_capacity=None):
         """The library's own tap tables (i2i_lanczos_tables, host code): (ksize, bounds int32 [out, 2], coeffs int32 [out, capacity]) as numpy

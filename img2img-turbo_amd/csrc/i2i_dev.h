@@ -156,6 +156,16 @@ __device__ __forceinline__ void agent_or_u32(uint32_t* p, uint32_t v) { *p |= v;
 __device__ __forceinline__ void agent_or_u32(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
 
+// the byte histogram of the automatic Canny thresholds (canny_hist_kernel, resize.hip): counts in LDS shared by the lanes of a wave
+// (ds_add_u32, no return), then one no-return add per non-zero bin into the image's 256 words of workspace.  Integer adds commute.
+#ifdef I2I_EMU
+__device__ __forceinline__ void lds_add_u32(uint32_t* p, uint32_t v) { *p += v; }
+__device__ __forceinline__ void agent_add_u32(uint32_t* p, uint32_t v) { *p += v; }
+#else
+__device__ __forceinline__ void lds_add_u32(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void agent_add_u32(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#endif
+
 // ---- arithmetic of the seeded noise op (randn_kernel, elementwise.hip): the high half of a 32 x 32 bit product (v_mul_hi_u32) and the
 // pi-scaled trigonometric functions (exact argument reduction: no fp32 product with pi).  The host has neither: the emulator reduces
 // the argument (in [0, 2)) to a multiple of 1/2 plus |r| <= 1/4 exactly and evaluates in double, well inside the 1 ulp of the device's.

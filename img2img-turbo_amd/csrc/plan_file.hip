@@ -103,7 +103,10 @@ const std::vector<size_t>& ptr_fields(int opcode) {
                                                       PF(resize_u8_ragged, tables), PF(resize_u8_ragged, bad_mask)};
     static const std::vector<size_t> scan_batch = {PF(scan_batch, x), PF(scan_batch, rec)};
     static const std::vector<size_t> scan_verdict = {PF(scan_verdict, rec), PF(scan_verdict, verdict)};
+    static const std::vector<size_t> canny_auto = {PF(canny_auto_thr, src), PF(canny_auto_thr, sigma_q16), PF(canny_auto_thr, thr),
+                                                   PF(canny_auto_thr, median2), PF(canny_auto_thr, ws)};
     switch (opcode) {
+        case I2I_OP_CANNY_AUTO_THR: return canny_auto;
         case I2I_OP_SCAN_BATCH: return scan_batch;
         case I2I_OP_SCAN_VERDICT: return scan_verdict;
         case I2I_OP_RESIZE_U8_RAGGED: return resize_ragged;

@@ -254,13 +254,27 @@ __global__ __launch_bounds__(256) void resize_ragged_u8_kernel(const i2i_resize_
     }
 }
 
-// Pillow's filter (src/libImaging/Resample.c: sinc_filter, lanczos_filter)
+// Pillow's filters (src/libImaging/Resample.c: sinc_filter, lanczos_filter, bicubic_filter)
 inline double lanczos_sinc(double x) {
     if (x == 0.0) return 1.0;
     x = x * 3.14159265358979323846;
     return sin(x) / x;
 }
 inline double lanczos_weight(double x) { return (-3.0 <= x && x < 3.0) ? lanczos_sinc(x) * lanczos_sinc(x / 3) : 0.0; }
+// Keys' cubic with a = -0.5, statement for statement as Pillow evaluates it (no fused multiply-add: the weights are rounded to 22 bits)
+inline double bicubic_weight(double x) {
+#pragma clang fp contract(off)
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+struct resample_filter { double (*weight)(double); double support; };
+inline const resample_filter* resample_filter_of(int filter) {
+    static const resample_filter lanczos = {lanczos_weight, 3.0}, bicubic = {bicubic_weight, 2.0};
+    return filter == I2I_FILTER_LANCZOS ? &lanczos : (filter == I2I_FILTER_BICUBIC ? &bicubic : nullptr);
+}
 
 }  // namespace
 
@@ -283,22 +297,24 @@ extern "C" int i2i_resize_u8_ragged(const i2i_resize_u8_ragged_params* p, int dt
     return i2i::check_launch("resize_u8_ragged");
 }
 
-extern "C" int i2i_lanczos_ksize(int in_size, int out_size) {
-    if (in_size < 1 || out_size < 1) return i2i::fail(I2I_ERR_BAD_ARG, "lanczos_ksize: sizes must be >= 1");
-    const double scale = (double)in_size / out_size, support = 3.0 * (scale < 1.0 ? 1.0 : scale);
+// `what` names the entry in error messages (i2i_lanczos_* are the LANCZOS case of i2i_resample_*)
+static int resample_ksize(const char* what, const resample_filter* f, int in_size, int out_size) {
+    if (!f) return i2i::fail(I2I_ERR_BAD_ARG, "%s_ksize: unknown filter", what);
+    if (in_size < 1 || out_size < 1) return i2i::fail(I2I_ERR_BAD_ARG, "%s_ksize: sizes must be >= 1", what);
+    const double scale = (double)in_size / out_size, support = f->support * (scale < 1.0 ? 1.0 : scale);
     return (int)ceil(support) * 2 + 1;
 }
 
-// precompute_coeffs + normalize_coeffs_8bpc, statement for statement as image_ops.lanczos_coeffs; a fused multiply-add in
+// precompute_coeffs + normalize_coeffs_8bpc, statement for statement as image_ops.resample_coeffs; a fused multiply-add in
 // `center - support + 0.5` or in the weight's argument would move tap windows, so contraction stays off here whatever the flags say
-extern "C" int i2i_lanczos_tables(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity) {
+static int resample_tables(const char* what, const resample_filter* f, int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity) {
 #pragma clang fp contract(off)
-    if (!bounds || !coeffs) return i2i::fail(I2I_ERR_BAD_ARG, "lanczos_tables: null pointer");
-    const int ksize = i2i_lanczos_ksize(in_size, out_size);
+    if (!bounds || !coeffs) return i2i::fail(I2I_ERR_BAD_ARG, "%s_tables: null pointer", what);
+    const int ksize = resample_ksize(what, f, in_size, out_size);
     if (ksize < 0) return ksize;
-    if (ksize_capacity < ksize) return i2i::fail(I2I_ERR_BAD_ARG, "lanczos_tables: ksize_capacity %d < ksize %d", ksize_capacity, ksize);
+    if (ksize_capacity < ksize) return i2i::fail(I2I_ERR_BAD_ARG, "%s_tables: ksize_capacity %d < ksize %d", what, ksize_capacity, ksize);
     const double scale = (double)in_size / out_size, filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 3.0 * filterscale, ss = 1.0 / filterscale;
+    const double support = f->support * filterscale, ss = 1.0 / filterscale;
     std::vector<double> kk((size_t)ksize);
     for (int xx = 0; xx < out_size; ++xx) {
         const double center = 0.0 + (xx + 0.5) * scale;
@@ -309,7 +325,7 @@ extern "C" int i2i_lanczos_tables(int in_size, int out_size, int32_t* bounds, in
         xmax -= xmin;
         double ww = 0.0;
         for (int x = 0; x < xmax; ++x) {
-            const double w = lanczos_weight(((double)(x + xmin) - center + 0.5) * ss);
+            const double w = f->weight(((double)(x + xmin) - center + 0.5) * ss);
             kk[x] = w;
             ww += w;
         }
@@ -323,6 +339,15 @@ extern "C" int i2i_lanczos_tables(int in_size, int out_size, int32_t* bounds, in
         bounds[2 * xx + 1] = xmax;
     }
     return ksize;
+}
+
+extern "C" int i2i_lanczos_ksize(int in_size, int out_size) { return resample_ksize("lanczos", resample_filter_of(I2I_FILTER_LANCZOS), in_size, out_size); }
+extern "C" int i2i_lanczos_tables(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity) {
+    return resample_tables("lanczos", resample_filter_of(I2I_FILTER_LANCZOS), in_size, out_size, bounds, coeffs, ksize_capacity);
+}
+extern "C" int i2i_resample_ksize(int filter, int in_size, int out_size) { return resample_ksize("resample", resample_filter_of(filter), in_size, out_size); }
+extern "C" int i2i_resample_tables(int filter, int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity) {
+    return resample_tables("resample", resample_filter_of(filter), in_size, out_size, bounds, coeffs, ksize_capacity);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -660,4 +685,140 @@ extern "C" int i2i_canny_u8_batch(const i2i_canny_u8_batch_params* p, int dtype,
     q.thr_dev = p->thr;
     q.ws = p->ws;
     return canny_launch("canny_u8_batch", &q, 2, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Automatic per-image Canny thresholds (i2i_canny_auto_thr, the contract is the comment of i2i_canny_auto_thr_params in include/i2i_turbo.h):
+// the median rule on the byte histogram of every image, written into the {low, high} table canny_nms_kernel reads.  Three launches:
+//   1 canny_hist_clear_kernel  ws[n][256] = 0
+//   2 canny_hist_kernel        grid (slices of an image, images), capped in total like scan_batch_kernel (elementwise.hip); a workgroup
+//                              works on one image at a time: 16-byte loads on the image's aligned part, byte loads on its head and tail (the
+//                              split comes from THAT image's start address), counts into one 256-bin copy per wave in LDS (a photograph puts
+//                              most bytes into a few neighbouring bins: one shared copy serialises on them), then one agent-scope add per
+//                              non-zero bin into the image's row of ws
+//   3 canny_select_kernel      one wave per image: lane l owns bins 4l .. 4l + 3, inclusive wave scan of the lane totals, the two middle
+//                              ranks, the formula, plain stores
+// Images with a negative sigma (manual sliders) are skipped by 2 and 3.
+namespace {
+
+constexpr int HIST_THREADS = 256, HIST_WAVES = HIST_THREADS / 64;
+constexpr int HIST_MAX_GRID = 1024;                          // workgroups of one launch at most (as SCAN_BATCH_MAX_GRID)
+constexpr int HIST_CHUNKS_PER_WG = 1024;                     // 16-byte chunks a workgroup is sized for (4 per lane)
+
+__global__ __launch_bounds__(256) void canny_hist_clear_kernel(uint32_t* hist, int64_t words) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) hist[i] = 0;
+}
+
+__device__ __forceinline__ void hist_word(uint32_t* mine, uint32_t v) {
+    lds_add_u32(mine + (v & 0xff), 1);
+    lds_add_u32(mine + ((v >> 8) & 0xff), 1);
+    lds_add_u32(mine + ((v >> 16) & 0xff), 1);
+    lds_add_u32(mine + (v >> 24), 1);
+}
+
+__global__ __launch_bounds__(HIST_THREADS) void canny_hist_kernel(const i2i_canny_auto_thr_params p) {
+    uint32_t* lds = (uint32_t*)i2i_smem;                     // [HIST_WAVES][256]
+    const int tid = (int)threadIdx.x;
+    uint32_t* mine = lds + (tid >> 6) * 256;
+    const int64_t N = (int64_t)p.h * p.w * p.c;
+    uint32_t* hist = (uint32_t*)p.ws;
+    for (int b = (int)blockIdx.y; b < p.n; b += (int)gridDim.y) {
+        if (p.sigma_q16[b] < 0) continue;                    // (the same verdict in every lane: no barrier is skipped by a part of the workgroup)
+#pragma unroll
+        for (int w = 0; w < HIST_WAVES; ++w) lds[w * 256 + tid] = 0;
+        __syncthreads();
+        const uint8_t* __restrict__ x = (const uint8_t*)p.src + (int64_t)b * N;
+        const int64_t mis = (int64_t)((uintptr_t)x & 15);
+        const int64_t head = mis ? (16 - mis < N ? 16 - mis : N) : 0;
+        const int64_t nb = (N - head) / 16, tail = N - head - nb * 16;
+        const u32x4* __restrict__ body = (const u32x4*)(x + head);
+        for (int64_t i = (int64_t)blockIdx.x * HIST_THREADS + tid; i < nb; i += (int64_t)gridDim.x * HIST_THREADS) {
+            const u32x4 v = body[i];
+            hist_word(mine, v[0]);
+            hist_word(mine, v[1]);
+            hist_word(mine, v[2]);
+            hist_word(mine, v[3]);
+        }
+        // the < 16 bytes in front of the first 16-byte boundary and the < 16 behind the last whole chunk
+        for (int64_t i = (int64_t)blockIdx.x * HIST_THREADS + tid; i < head + tail; i += (int64_t)gridDim.x * HIST_THREADS)
+            lds_add_u32(mine + x[i < head ? i : i + nb * 16], 1);
+        __syncthreads();
+        uint32_t tot = 0;
+#pragma unroll
+        for (int w = 0; w < HIST_WAVES; ++w) tot += lds[w * 256 + tid];
+        if (tot) agent_add_u32(hist + (int64_t)b * 256 + tid, tot);
+        __syncthreads();                                     // the copies are free again before the next image of this workgroup zeroes them
+    }
+}
+
+// value of 0-based rank r, if it lies in this lane's four bins (lo = count of bytes below the lane's first bin), else 0: exactly one
+// lane of the wave finds it, so the wave sum of the returns is the value
+__device__ __forceinline__ int select_rank(const uint32_t c[4], uint32_t lo, uint32_t r, int first_bin) {
+    int v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (r >= lo && r < lo + c[k]) v = first_bin + k;
+        lo += c[k];
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void canny_select_kernel(const i2i_canny_auto_thr_params p) {
+    const int lane = (int)threadIdx.x;
+    const uint32_t N = (uint32_t)((int64_t)p.h * p.w * p.c);
+    for (int b = (int)blockIdx.x; b < p.n; b += (int)gridDim.x) {
+        int s = p.sigma_q16[b];
+        if (s < 0) continue;
+        s = s > 65536 ? 65536 : s;
+        const uint32_t* row = (const uint32_t*)p.ws + (int64_t)b * 256 + 4 * lane;
+        const uint32_t c[4] = {row[0], row[1], row[2], row[3]};
+        uint32_t incl = c[0] + c[1] + c[2] + c[3];
+        const uint32_t own = incl;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {                   // inclusive scan over the lanes
+            const uint32_t o = __shfl(incl, (lane - d) & 63);
+            if (lane >= d) incl += o;
+        }
+        int ab = select_rank(c, incl - own, (N - 1) / 2, 4 * lane) + select_rank(c, incl - own, N / 2, 4 * lane);
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) ab += __shfl_xor(ab, m);
+        if (lane == 0) {
+            const int m2 = ab;                               // 0 .. 510: both products below fit in int32
+            const int low = (m2 * (65536 - s)) >> 17, high = (m2 * (65536 + s)) >> 17;
+            p.thr[2 * b] = low < 0 ? 0 : low;
+            p.thr[2 * b + 1] = high > 255 ? 255 : high;
+            if (p.median2) p.median2[b] = (uint32_t)m2;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t i2i_canny_auto_ws_bytes(int n) { return n < 1 ? 0 : (size_t)n * 256 * sizeof(uint32_t); }
+
+extern "C" int i2i_canny_auto_thr(const i2i_canny_auto_thr_params* p, int dtype, void* stream) {
+    (void)dtype;
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: null pointer");
+    if (p->c < 1 || p->c > 4) return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: c = %d outside 1..4", p->c);
+    if (p->n < 0 || p->h < 0 || p->w < 0) return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: negative size (n = %d, h = %d, w = %d)", p->n, p->h, p->w);
+    if (p->n == 0) return I2I_OK;
+    if (p->h == 0 || p->w == 0) return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: empty images (h = %d, w = %d) have no median", p->h, p->w);
+    const int64_t N = (int64_t)p->h * p->w * p->c;           // (h * w < 2^62, c <= 4: no overflow)
+    if (N > 0x7fffffff) return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: more than 2^31 - 1 bytes per image (the bins are 32-bit counts)");
+    if (!p->src || !p->sigma_q16 || !p->thr || !p->ws) return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: null pointer (src, sigma_q16, thr, ws)");
+    if (((uintptr_t)p->sigma_q16 | (uintptr_t)p->thr | (uintptr_t)p->median2) & 3)
+        return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: sigma_q16, thr and median2 must be 4-byte aligned");
+    if ((uintptr_t)p->ws & 15) return i2i::fail(I2I_ERR_BAD_ARG, "canny_auto_thr: the workspace must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t words = (int64_t)p->n * 256;
+    const int64_t cb = (words + 255) / 256;
+    hipLaunchKernelGGL(canny_hist_clear_kernel, dim3((unsigned)(cb < HIST_MAX_GRID ? cb : HIST_MAX_GRID)), dim3(256), 0, s, (uint32_t*)p->ws, words);
+    // slices per image: what the chunk loop of one image can use, then the cap on the whole grid
+    const int64_t want = (N / 16 + HIST_CHUNKS_PER_WG - 1) / HIST_CHUNKS_PER_WG;
+    const unsigned gy = (unsigned)(p->n < HIST_MAX_GRID ? p->n : HIST_MAX_GRID);
+    const int64_t cap = HIST_MAX_GRID / gy;
+    const unsigned gx = (unsigned)(want < 1 ? 1 : (want > cap ? cap : want));
+    hipLaunchKernelGGL(canny_hist_kernel, dim3(gx, gy), dim3(HIST_THREADS), HIST_WAVES * 256 * sizeof(uint32_t), s, *p);
+    hipLaunchKernelGGL(canny_select_kernel, dim3(gy), dim3(64), 0, s, *p);
+    return i2i::check_launch("canny_auto_thr");
 }

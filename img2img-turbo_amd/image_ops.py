@@ -35,12 +35,32 @@ def _lanczos(x):
     return 0.0
 
 
-@functools.lru_cache(maxsize=64)
-def lanczos_coeffs(in_size, out_size):
-    """Pillow's per-output-coordinate tap window and weights for one axis: (ksize, bounds int32 [out, 2], weights int32 [out, ksize])."""
+def _bicubic(x):
+    """Pillow's bicubic_filter (Keys' cubic, a = -0.5), evaluated in its order of operations."""
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+FILTERS = {"lanczos": (_lanczos, 3.0), "bicubic": (_bicubic, 2.0)}      # name -> (weight function, support), as Pillow's `struct filter`
+
+
+@functools.lru_cache(maxsize=128)
+def resample_coeffs(in_size, out_size, filter="lanczos"):
+    """Pillow's per-output-coordinate tap window and weights for one axis under ``filter`` ("lanczos": Image.LANCZOS; "bicubic":
+    Image.BICUBIC, the default of ``Image.resize`` -- what gradio_canny2image.py:16 gets by passing no filter):
+    (ksize, bounds int32 [out, 2], weights int32 [out, ksize])."""
+    if filter not in FILTERS:
+        raise ValueError("resample filter %r (supported: %s)" % (filter, ", ".join(sorted(FILTERS))))
+    weight, filter_support = FILTERS[filter]
     scale = float(in_size) / out_size
     filterscale = max(scale, 1.0)
-    support = 3.0 * filterscale
+    support = filter_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     kk = np.zeros((out_size, ksize), dtype=np.float64)
     bounds = np.zeros((out_size, 2), dtype=np.int32)
@@ -51,7 +71,7 @@ def lanczos_coeffs(in_size, out_size):
         xmax = min(int(center + support + 0.5), in_size) - xmin
         ww = 0.0
         for x in range(xmax):
-            w = _lanczos((x + xmin - center + 0.5) * ss)
+            w = weight((x + xmin - center + 0.5) * ss)
             kk[xx, x] = w
             ww += w
         if ww != 0.0:
@@ -63,28 +83,35 @@ def lanczos_coeffs(in_size, out_size):
     return ksize, bounds, ik
 
 
+def lanczos_coeffs(in_size, out_size):
+    """``resample_coeffs(in_size, out_size, "lanczos")``: Pillow's LANCZOS tap windows and weights for one axis."""
+    return resample_coeffs(in_size, out_size, "lanczos")
+
+
 import collections
 import contextlib
 
-_DEV_TABLES = collections.OrderedDict()      # (in, out, device) -> coefficient tables on the device; small LRU: a server fed
+_DEV_TABLES = collections.OrderedDict()      # (in, out, device[, filter]) -> coefficient tables on the device; small LRU: a server fed
 _DEV_TABLES_MAX = 64                         # arbitrary input sizes must not grow device memory without bound
 
 
-def _tables(in_size, out_size, device):
-    key = (in_size, out_size, str(device))
+def _tables(in_size, out_size, device, resample="lanczos"):
+    key = (in_size, out_size, str(device)) + (() if resample == "lanczos" else (resample,))
     if key in _DEV_TABLES:
         _DEV_TABLES.move_to_end(key)
     else:
-        ksize, b, k = lanczos_coeffs(in_size, out_size)
+        ksize, b, k = resample_coeffs(in_size, out_size, resample)
         _DEV_TABLES[key] = (ksize, torch.from_numpy(b.copy()).to(device), torch.from_numpy(k.copy()).to(device))
         while len(_DEV_TABLES) > _DEV_TABLES_MAX:
             _DEV_TABLES.popitem(last=False)
     return _DEV_TABLES[key]
 
 
-def lanczos_resize_u8(images, size, lib=None):
+def lanczos_resize_u8(images, size, lib=None, *, resample="lanczos"):
     """images: uint8 [N, H, W, C] (C <= 4) on the device -> uint8 [N, size[1], size[0], C]; ``size`` = (width, height) as PIL takes it.
-    Bit-identical to ``Image.resize(size, Image.LANCZOS)`` per image.  Asynchronous on the current stream."""
+    Bit-identical to ``Image.resize(size, Image.LANCZOS)`` per image.  Asynchronous on the current stream.
+    ``resample="bicubic"``: the same passes on Pillow's BICUBIC tables, bit-identical to ``Image.resize(size)`` (Pillow's default filter:
+    gradio_canny2image.py:16)."""
     assert images.dtype == torch.uint8 and images.dim() == 4 and images.shape[-1] <= 4
     lib = lib or _capi.default_library()
     n, h, w, c = images.shape
@@ -99,7 +126,7 @@ def lanczos_resize_u8(images, size, lib=None):
         for axis, n_in, n_out in ((1, w, ow), (0, h, oh)):          # Pillow's order: horizontal pass, then vertical pass
             if n_in == n_out:
                 continue
-            ksize, bounds, coeffs = _tables(n_in, n_out, dev)
+            ksize, bounds, coeffs = _tables(n_in, n_out, dev, resample)
             hin, win = cur.shape[1], cur.shape[2]
             out = torch.empty((n, hin, n_out, c) if axis == 1 else (n, n_out, win, c), dtype=torch.uint8, device=dev)
             p = _capi.ResizeU8Params()
@@ -181,26 +208,28 @@ _RAGGED_POOLS = collections.OrderedDict()    # (sizes in, sizes out, c, library,
 _RAGGED_POOLS_MAX = 16
 
 
-def _ragged_pool(lib, in_hw, out_wh, c, device):
-    key = (tuple(in_hw), tuple(out_wh), c, lib.path, str(device))
+def _ragged_pool(lib, in_hw, out_wh, c, device, resample="lanczos"):
+    key = (tuple(in_hw), tuple(out_wh), c, lib.path, str(device)) + (() if resample == "lanczos" else (resample,))
     if key in _RAGGED_POOLS:
         _RAGGED_POOLS.move_to_end(key)
     else:
-        layout = ragged_layout(in_hw, out_wh, c, tables_of=lib.lanczos_tables)
+        layout = ragged_layout(in_hw, out_wh, c, tables_of=lib.lanczos_tables if resample == "lanczos" else functools.partial(lib.resample_tables, resample))
         _RAGGED_POOLS[key] = (layout,) + ragged_upload(layout, device)
         while len(_RAGGED_POOLS) > _RAGGED_POOLS_MAX:
             _RAGGED_POOLS.popitem(last=False)
     return _RAGGED_POOLS[key]
 
 
-def lanczos_resize_u8_ragged(images, size, lib=None):
+def lanczos_resize_u8_ragged(images, size, lib=None, *, resample="lanczos"):
     """LANCZOS resize of a batch whose images differ in size, in TWO launches whatever the batch holds (i2i_resize_u8_ragged; the eager
     lanczos_resize_u8 is two launches and two allocations per distinct size).
     ``images``: a list of uint8 HWC tensors [H_b, W_b, C] on one device (same C <= 4), or one stacked uint8 [N, H, W, C].
     ``size``: one (width, height) for every image -> a stacked uint8 [N, height, width, C]; or a list of N (width, height) -> a list of
     uint8 [height_b, width_b, C] tensors (views of one arena).  Image b is bit-identical to ``lanczos_resize_u8(images[b][None], size_b)``,
     hence (C = 1, 3) to ``Image.resize(size_b, Image.LANCZOS)``.  Asynchronous on the current stream; the tap tables come from the
-    library's i2i_lanczos_tables and are cached per set of sizes."""
+    library's i2i_lanczos_tables and are cached per set of sizes.  ``resample="bicubic"``: Pillow's BICUBIC tables (i2i_resample_tables)."""
+    if resample not in FILTERS:
+        raise ValueError("resample filter %r (supported: %s)" % (resample, ", ".join(sorted(FILTERS))))
     lib = lib or _capi.default_library()
     stacked_in = torch.is_tensor(images)
     if stacked_in:
@@ -225,7 +254,7 @@ def lanczos_resize_u8_ragged(images, size, lib=None):
     in_hw = [(int(t.shape[0]), int(t.shape[1])) for t in items]
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
     with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
-        layout, desc_dev, tables_dev = _ragged_pool(lib, in_hw, out_wh, c, dev)
+        layout, desc_dev, tables_dev = _ragged_pool(lib, in_hw, out_wh, c, dev, resample)
         nb = in_hw[0][0] * in_hw[0][1] * c
         if stacked_in and nb % 4 == 0 and images.is_contiguous() and images.data_ptr() % 4 == 0:
             src = images.view(-1)                                                # already an arena: dense images at 4-byte aligned offsets
@@ -254,13 +283,35 @@ def canny_thresholds(low, high):
     return int(math.floor(low)), int(math.floor(high))
 
 
-def canny_u8(images, low=100, high=200, out_channels=3, lib=None):
-    """images: uint8 [N, H, W, C] (C <= 4) on the device -> uint8 [N, H, W, out_channels] (1 or 3), 255 on edges: ``cv2.Canny(img, low,
-    high)`` (aperture 3, L1 gradient) per image, replicated over the channels as ``canny_from_pil`` does (src/image_prep.py:6-12).  The
-    contract is spelled out at i2i_canny_u8_params (include/i2i_turbo.h), tests/canny_ref.py is its CPU oracle; parity with OpenCV itself is
-    unpinned where cv2 is not installed.  Asynchronous on the current stream (five launches in csrc/resize.hip, no read-back).
-    ``low`` / ``high`` may also be sequences of N values, one pair per image (i2i_canny_u8_batch_params: image b of the result is what a
-    call on image b alone with its pair gives, bit for bit); a scalar beside a sequence holds for every image."""
+def sigma_to_q16(sigma):
+    """sigma of the median rule as the kernels take it (i2i_canny_auto_thr_params.sigma_q16): the one place this conversion lives."""
+    return int(round(sigma * 65536))
+
+
+def sigma_q16_list(sigma, n):
+    """``sigma`` (a scalar, or a sequence of n values whose None entries mean "leave that image's pair untouched") -> n int32 values;
+    None becomes -1, anything outside 0 .. 1 is refused."""
+    vals = list(sigma) if isinstance(sigma, (list, tuple)) else [sigma] * n
+    if len(vals) != n:
+        raise ValueError("%d sigma values for %d images" % (len(vals), n))
+    out = []
+    for v in vals:
+        if v is None:
+            out.append(-1)
+            continue
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError("sigma = %r outside 0 .. 1" % (v,))
+        out.append(sigma_to_q16(float(v)))
+    return out
+
+
+def canny_auto_thresholds(images, sigma=0.33, lib=None, *, thr=None):
+    """The median rule ("auto-Canny") on the device: images uint8 [N, H, W, C] (C <= 4) -> (thr int32 [N, 2] = {low, high} per image,
+    median2 uint32 bits [N] (an int32 tensor) = twice the median of ALL bytes of the image), both on the device, with
+    low = max(0, (1 - sigma) * median), high = min(255, (1 + sigma) * median) in the integer form of i2i_canny_auto_thr_params
+    (include/i2i_turbo.h; tests/canny_auto_ref.py is its CPU oracle).  The rule is not part of the reference, and sigma = 0.33 is its
+    customary default, not a tuned value.  ``sigma``: a scalar or a sequence of N; a None entry leaves that image's row of ``thr`` (zeros
+    unless the caller passes its own table) and of median2 untouched.  Asynchronous on the current stream: three launches, no read-back."""
     assert images.dtype == torch.uint8 and images.dim() == 4 and 1 <= images.shape[-1] <= 4
     lib = lib or _capi.default_library()
     n, h, w, c = images.shape
@@ -268,19 +319,57 @@ def canny_u8(images, low=100, high=200, out_channels=3, lib=None):
     dev = src.device
     assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
-    per_image = not all(isinstance(v, (int, float)) for v in (low, high))
-    if per_image:
+    sq = sigma_q16_list(sigma, n)
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        sig = torch.tensor(sq, dtype=torch.int32).to(dev)
+        if thr is None:
+            thr = torch.zeros(n, 2, dtype=torch.int32, device=dev)
+        assert thr.dtype == torch.int32 and thr.shape == (n, 2) and thr.is_contiguous() and thr.device == dev
+        med = torch.zeros(n, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(lib.canny_auto_ws_bytes(n), 16), dtype=torch.uint8, device=dev)
+        p = _capi.CannyAutoThrParams()
+        p.src, p.sigma_q16, p.thr, p.median2, p.ws = src.data_ptr(), sig.data_ptr(), thr.data_ptr(), med.data_ptr(), ws.data_ptr()
+        p.n, p.h, p.w, p.c = n, h, w, c
+        lib.check(lib.lib.i2i_canny_auto_thr(C.addressof(p), 0, stream))
+    return thr, med
+
+
+def canny_u8(images, low=100, high=200, out_channels=3, lib=None, *, sigma=0.33):
+    """images: uint8 [N, H, W, C] (C <= 4) on the device -> uint8 [N, H, W, out_channels] (1 or 3), 255 on edges: ``cv2.Canny(img, low,
+    high)`` (aperture 3, L1 gradient) per image, replicated over the channels as ``canny_from_pil`` does (src/image_prep.py:6-12).  The
+    contract is spelled out at i2i_canny_u8_params (include/i2i_turbo.h), tests/canny_ref.py is its CPU oracle; parity with OpenCV itself is
+    unpinned where cv2 is not installed.  Asynchronous on the current stream (five launches in csrc/resize.hip, no read-back).
+    ``low`` / ``high`` may also be sequences of N values, one pair per image (i2i_canny_u8_batch_params: image b of the result is what a
+    call on image b alone with its pair gives, bit for bit); a scalar beside a sequence holds for every image.
+    ``low="auto"``: the thresholds come from the images themselves (canny_auto_thresholds with ``sigma``, a scalar or one per image) and feed
+    the per-image entry without leaving the device; ``high`` is ignored."""
+    assert images.dtype == torch.uint8 and images.dim() == 4 and 1 <= images.shape[-1] <= 4
+    lib = lib or _capi.default_library()
+    n, h, w, c = images.shape
+    src = images.contiguous()
+    dev = src.device
+    assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+    auto = isinstance(low, str)
+    if auto:
+        if low != "auto":
+            raise ValueError("canny_u8: low = %r (a number, a sequence, or \"auto\")" % (low,))
+        if any(v is None for v in (sigma if isinstance(sigma, (list, tuple)) else [sigma])):
+            raise ValueError("canny_u8(low=\"auto\"): every image needs a sigma (None has no pair to fall back to here)")
+        thr_auto, _ = canny_auto_thresholds(src, sigma, lib)
+    per_image = auto or not all(isinstance(v, (int, float)) for v in (low, high))
+    if per_image and not auto:
         lows, highs = [(list(v) if not isinstance(v, (int, float)) else [v] * n) for v in (low, high)]
         if len(lows) != n or len(highs) != n:
             raise ValueError("canny_u8: %d low / %d high thresholds for %d images" % (len(lows), len(highs), n))
         pairs = [canny_thresholds(a, b) for a, b in zip(lows, highs)]
-    else:
+    elif not auto:
         lo, hi = canny_thresholds(low, high)
     with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
         out = torch.empty((n, h, w, int(out_channels)), dtype=torch.uint8, device=dev)
         ws = torch.empty(max(lib.canny_ws_bytes(n, h, w), 16), dtype=torch.uint8, device=dev)
         if per_image:
-            thr = torch.tensor(pairs, dtype=torch.int32).reshape(n, 2).to(dev)
+            thr = thr_auto if auto else torch.tensor(pairs, dtype=torch.int32).reshape(n, 2).to(dev)
             q = _capi.CannyU8BatchParams()
             q.src, q.dst, q.ws, q.thr = src.data_ptr(), out.data_ptr(), ws.data_ptr(), thr.data_ptr()
             q.n, q.h, q.w, q.c, q.out_c = n, h, w, c, int(out_channels)
@@ -293,10 +382,10 @@ def canny_u8(images, low=100, high=200, out_channels=3, lib=None):
     return out
 
 
-def resize_to_multiple_of_8(images, lib=None):
+def resize_to_multiple_of_8(images, lib=None, *, resample="lanczos"):
     """src/inference_paired.py:38-41 on the device: LANCZOS resize to (w - w % 8, h - h % 8)."""
     h, w = images.shape[1], images.shape[2]
-    return lanczos_resize_u8(images, (w - w % 8, h - h % 8), lib)
+    return lanczos_resize_u8(images, (w - w % 8, h - h % 8), lib, resample=resample)
 
 
 def apply_image_prep(images, image_prep, lib=None):

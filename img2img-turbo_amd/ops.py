@@ -184,6 +184,16 @@ def canny_u8_batch(src, dst, ws, thr, *, n, h, w, c, out_c=3):
     return K.OP_CANNY_U8_BATCH, _keep(p, src, dst, ws, thr)
 
 
+def canny_auto_thr(src, sigma_q16, thr, ws, *, n, h, w, c, median2=None):
+    """thr[b] = {low, high} of the median rule on image b of the uint8 HWC batch src[n, h, w, c] (i2i_canny_auto_thr_params): ``sigma_q16``
+    device int32 [n] (sigma * 65536, negative = leave thr[b] as it is), ``thr`` device int32 [n, 2] -- the table canny_u8_batch reads --,
+    ``median2`` optional device int32 / uint32 [n], ``ws``: a uint8 tensor of at least Library.canny_auto_ws_bytes(n) bytes."""
+    p = K.CannyAutoThrParams()
+    p.src, p.sigma_q16, p.thr, p.median2, p.ws = ptr(src), ptr(sigma_q16), ptr(thr), ptr(median2), ptr(ws)
+    p.n, p.h, p.w, p.c = int(n), int(h), int(w), int(c)
+    return K.OP_CANNY_AUTO_THR, _keep(p, src, sigma_q16, thr, median2, ws)
+
+
 def resize_u8_ragged(src, dst, images, tables, *, n, c, axis, grid_units, bad_mask=None, src_bytes=None, dst_bytes=None, tables_len=None,
                      first_image=0):
     """One separable LANCZOS pass over a ragged batch (i2i_resize_u8_ragged_params): ``src`` / ``dst`` are uint8 arenas, ``images`` a device

@@ -210,11 +210,13 @@ class TurboGeneratorBase(torch.nn.Module):
         "eps" (and "noise") itself from the plan's device state (ForwardPlan.set_seed; the contract of i2i_randn_params) and advances the step
         after every run; again only the boolean is part of the key, every seed shares the plan.  ``rng="per_image"`` / ``canny="per_image"``:
         one noise state / one threshold pair per image of the batch (ForwardPlan.set_seeds, set_canny_thresholds with sequences; the
-        contracts of i2i_randn_batch_params / i2i_canny_u8_batch_params).  The mode is part of the key, so the plans of scalar callers stay
-        theirs."""
+        contracts of i2i_randn_batch_params / i2i_canny_u8_batch_params).  ``canny="auto"``: the per-image form whose thresholds the program
+        computes from the photos (ForwardPlan.set_canny_sigma; the contract of i2i_canny_auto_thr_params).  The mode is part of the key, so
+        the plans of scalar callers stay theirs."""
         r_plan = float(r) if stochastic else 1.0
         self.set_lora_scale(r_plan)
-        key = ((B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io) + ((("canny_per_image",) if canny == "per_image" else (True,)) if canny else ())
+        key = ((B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io)
+               + ((("canny_per_image",) if canny == "per_image" else (("canny_auto",) if canny == "auto" else (True,))) if canny else ())
                + ((("rng_per_image",) if rng == "per_image" else ("rng",)) if rng else ())
                + (("health", self.health, self.health_limit) if self.health else ()) + (("health_per_image",) if self.health_per_image else ()))
         if key in self._plans:
@@ -224,7 +226,7 @@ class TurboGeneratorBase(torch.nn.Module):
             if u8_io is not None:
                 opts["u8_io"] = u8_io
             if canny:
-                opts["canny"] = canny if canny == "per_image" else True
+                opts["canny"] = canny if canny in ("per_image", "auto") else True
             if rng:
                 opts["rng"] = rng if rng == "per_image" else True
             if self.health:
@@ -279,7 +281,12 @@ class TurboGeneratorBase(torch.nn.Module):
                 plan.set_seeds(seed, 0)
             elif seed is not None:
                 plan.set_seed(seed, 0)
-            if canny is not None:
+            if canny is not None and canny[0] == "auto":
+                _, sigmas, lows, highs = canny
+                plan.set_canny_sigma(sigmas)
+                if any(v is not None for v in lows):
+                    plan.set_canny_thresholds(lows, highs)
+            elif canny is not None:
                 plan.set_canny_thresholds(*canny)
             if self.use_graph:
                 plan.replay()
@@ -300,10 +307,41 @@ def seed_argument(seed, B):
 
 
 def per_image_mode(canny):
-    """get_plan's canny mode of forward_u8's normalised ``canny``: None -> False, (low, high) -> True, (lows, highs) -> "per_image"."""
+    """get_plan's canny mode of forward_u8's normalised ``canny``: None -> False, (low, high) -> True, (lows, highs) -> "per_image",
+    ("auto", sigmas, lows, highs) -> "auto"."""
     if canny is None:
         return False
+    if canny[0] == "auto":
+        return "auto"
     return "per_image" if isinstance(canny[0], list) else True
+
+
+def _is_auto(entry):
+    """"auto" or ("auto", sigma): one automatic request of forward_u8's ``canny=``."""
+    return entry == "auto" if isinstance(entry, str) else (isinstance(entry, (tuple, list)) and len(entry) == 2 and entry[0] == "auto"
+                                                            and isinstance(entry[1], (int, float)))
+
+
+def canny_argument(canny, B, default_sigma=0.33):
+    """forward_u8's ``canny=`` in the form _execute takes: None | (low, high) | (lows, highs) | ("auto", sigmas, lows, highs) -- the last
+    with B entries each, sigmas[b] None for a request with its own sliders and lows[b] / highs[b] None for an automatic one."""
+    if canny is None or canny is False:
+        return None
+    if canny is True:
+        return (100, 200)
+    if _is_auto(canny):
+        sigma = default_sigma if isinstance(canny, str) else float(canny[1])
+        return ("auto", [sigma] * B, [None] * B, [None] * B)
+    if isinstance(canny, str):
+        raise ValueError("canny=%r (True, (low, high), \"auto\", (\"auto\", sigma) or a list of B such entries)" % (canny,))
+    if isinstance(canny[0], (int, float)):
+        return (canny[0], canny[1])
+    if len(canny) != B:                                                      # a sequence of B entries
+        raise ValueError("canny= holds %d entries for a batch of %d" % (len(canny), B))
+    if not any(_is_auto(e) for e in canny):
+        return ([p[0] for p in canny], [p[1] for p in canny])
+    sigmas = [(default_sigma if isinstance(e, str) else float(e[1])) if _is_auto(e) else None for e in canny]
+    return ("auto", sigmas, [None if _is_auto(e) else e[0] for e in canny], [None if _is_auto(e) else e[1] for e in canny])
 
 
 class Pix2Pix_Turbo(TurboGeneratorBase):
@@ -332,7 +370,7 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
             self.lora_rank_unet, self.lora_rank_vae = weights.meta["rank_unet"], weights.meta["rank_vae"]
 
     @torch.no_grad()
-    def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, **kw):
+    def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, return_edges=False, resample="lanczos", **kw):
         """uint8 HWC in, uint8 HWC out ([B, H, W, 3] on the device): the callers' ``F.to_tensor`` (src/inference_paired.py:50)
         and ``ToPILImage()(out*0.5+0.5)`` (:72) run inside the boundary kernels; everything else as ``forward``.
         ``resize="multiple_of_8"`` first applies the script's ``input_image.resize((w - w % 8, h - h % 8), Image.LANCZOS)``
@@ -345,6 +383,15 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         Every (low, high) runs the same plan / captured graph (the thresholds are device state).  OpenCV parity is unpinned where cv2 is
         absent: tests/canny_ref.py is the oracle of the contract in include/i2i_turbo.h.  ``canny=[(low, high)] * B``: one pair per image (the
         requests of a batch keep their own sliders; image b is what a call on image b alone gives, i2i_canny_u8_batch_params).
+        ``canny="auto"`` / ``canny=("auto", sigma)``: the thresholds are computed on the device from each photo by the median rule, low =
+        (1 - sigma) * median, high = (1 + sigma) * median in the integer form of i2i_canny_auto_thr_params (include/i2i_turbo.h) -- the first
+        op of the program, in front of Canny.  The rule is NOT part of the reference; sigma = 0.33 is its customary default, not a tuned one.
+        Per image, ``canny=[(100, 200), "auto", ("auto", 0.25), ..]`` mixes requests with their own sliders and automatic ones on one plan.
+        ``return_edges=True`` (with ``canny``): returns ``(out, edges)``, edges a uint8 [B, H, W, 3] clone of the edge map the generator saw
+        (255 on edges; the reference saves and shows ``255 - edges``, src/inference_paired.py:48-49) -- and on an automatic plan ``(out,
+        edges, thr)``, thr int32 [B, 2] the {low, high} pairs that were used.
+        ``resample="bicubic"``: the resize uses Pillow's BICUBIC tables, bit-identical to ``Image.resize(size)`` with no filter argument
+        (gradio_canny2image.py:16); the default is the scripts' LANCZOS.
         ``seed=``: as in ``forward``.
         ``images_u8`` may also be a LIST of uint8 [H_b, W_b, 3] tensors of different sizes with ``resize=(width, height)``: the requests of a
         batch are brought to the model size in two launches (image_ops.lanczos_resize_u8_ragged) and image b of the result is what the
@@ -355,25 +402,25 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
                 raise ValueError("a list of images of different sizes needs resize=(width, height): resize=%r leaves them at different sizes" % (resize,))
             from .image_ops import lanczos_resize_u8_ragged
             with self._on_device():
-                images_u8 = lanczos_resize_u8_ragged(list(images_u8), (int(resize[0]), int(resize[1])), self.lib)
+                images_u8 = lanczos_resize_u8_ragged(list(images_u8), (int(resize[0]), int(resize[1])), self.lib, resample=resample)
             resize = None
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
-        if canny is not None and canny is not False:
-            if sketch:
-                raise ValueError("canny and sketch=True are the two exclusive branches of the script (src/inference_paired.py:47-58)")
-            if canny is not True and not isinstance(canny[0], (int, float)):      # a sequence of B pairs -> (lows, highs)
-                if len(canny) != images_u8.shape[0]:
-                    raise ValueError("canny= holds %d (low, high) pairs for a batch of %d" % (len(canny), images_u8.shape[0]))
-                canny = ([p[0] for p in canny], [p[1] for p in canny])
-            else:
-                canny = (100, 200) if canny is True else (canny[0], canny[1])
-        else:
-            canny = None
+        canny = canny_argument(canny, images_u8.shape[0])
+        if canny is not None and sketch:
+            raise ValueError("canny and sketch=True are the two exclusive branches of the script (src/inference_paired.py:47-58)")
+        if return_edges and canny is None:
+            raise ValueError("return_edges=True needs canny=: without it the input IS the edge map")
         if resize is not None:
             from .image_ops import lanczos_resize_u8, resize_to_multiple_of_8
             with self._on_device():
-                images_u8 = resize_to_multiple_of_8(images_u8, self.lib) if resize == "multiple_of_8" else lanczos_resize_u8(images_u8, resize, self.lib)
-        return self.forward(images_u8, *args, _u8_io=(1.0, 0.0, 128) if sketch else (1.0, 0.0), _canny=canny, **kw)
+                images_u8 = (resize_to_multiple_of_8(images_u8, self.lib, resample=resample) if resize == "multiple_of_8"
+                             else lanczos_resize_u8(images_u8, resize, self.lib, resample=resample))
+        out = self.forward(images_u8, *args, _u8_io=(1.0, 0.0, 128) if sketch else (1.0, 0.0), _canny=canny, **kw)
+        if not return_edges:
+            return out
+        plan = self._last_plan                   # (the plan that just ran; same stream, so the clones see this run's edge map)
+        with self._on_device():
+            return (out, plan.canny_edges.clone()) + ((plan.canny_thr.clone(),) if plan.canny_auto else ())
 
     @torch.no_grad()
     def forward(self, c_t, prompt=None, prompt_tokens=None, deterministic=True, r=1.0, noise_map=None,

@@ -184,15 +184,25 @@ class ForwardPlan:
         # csrc/resize.hip): x_in holds the photos, the boundary op reads the plan-owned edge maps.  The thresholds are DEVICE state
         # (canny_thr = {low, high}, read by the kernels at run time), so the program, its hipGraph and an exported plan file follow the
         # caller's sliders without re-planning.  canny="per_image": one pair per image (canny_thr int32 [B, 2], I2I_OP_CANNY_U8_BATCH) -- the
-        # requests a batching host packed into one replay keep their own sliders.
-        assert canny in (False, True, "per_image"), canny
-        self.canny = canny if canny == "per_image" else bool(canny)
-        self.canny_per_image = canny == "per_image"
+        # requests a batching host packed into one replay keep their own sliders.  canny="auto": the per-image form with I2I_OP_CANNY_AUTO_THR
+        # in front, which WRITES canny_thr from the photos (the median rule, the contract of i2i_canny_auto_thr_params) -- canny_sigma int32 [B]
+        # holds sigma * 65536 per image (set_canny_sigma; negative = that image keeps the pair set_canny_thresholds wrote), canny_median2
+        # (uint32 bits [B]) the doubled medians of the last run.  One plan serves a batch that mixes automatic and manual requests.
+        assert canny in (False, True, "per_image", "auto"), canny
+        self.canny = canny if canny in ("per_image", "auto") else bool(canny)
+        self.canny_auto = canny == "auto"
+        self.canny_per_image = canny in ("per_image", "auto")      # (the shape of canny_thr and the Canny op that reads it)
         assert not self.canny or u8_io, "canny needs the uint8 boundary (u8_io)"
         self.canny_thr = (torch.tensor([[100, 200]] * B if self.canny_per_image else [100, 200], dtype=torch.int32, device=device)
                           if self.canny else None)
         self.canny_edges = torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if self.canny else None
         self.canny_ws = torch.zeros(max(lib.canny_ws_bytes(B, H, W), 16), dtype=torch.uint8, device=device) if self.canny else None
+        self.canny_sigma = self.canny_median2 = self.canny_auto_ws = None
+        if self.canny_auto:
+            from .image_ops import sigma_to_q16
+            self.canny_sigma = torch.full((B,), sigma_to_q16(0.33), dtype=torch.int32, device=device)
+            self.canny_median2 = torch.zeros(B, dtype=torch.int32, device=device)
+            self.canny_auto_ws = torch.zeros(max(lib.canny_auto_ws_bytes(B), 16), dtype=torch.uint8, device=device)
         self.x_in = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
                      torch.zeros(B, 3, H, W, dtype=torch.float32, device=device))
         self.eps = torch.zeros(B, lat, h8, w8, dtype=torch.float32, device=device)
@@ -1154,6 +1164,9 @@ class ForwardPlan:
             if self.noise is not None:
                 self._add(O.randn(self.noise, state=self.rng_state, stream_id=STREAM_NOISE), "rng.noise", nbytes=self.noise.numel() * 4)
         src = self.x_in
+        if self.canny_auto:
+            self._add(O.canny_auto_thr(self.x_in, self.canny_sigma, self.canny_thr, self.canny_auto_ws, n=B, h=H, w=W, c=3, median2=self.canny_median2),
+                      "input.canny_auto_thr", nbytes=B * H * W * 3)
         if self.canny_per_image:
             self._add(O.canny_u8_batch(self.x_in, self.canny_edges, self.canny_ws, self.canny_thr, n=B, h=H, w=W, c=3, out_c=3), "input.canny",
                       nbytes=B * H * W * 6)
@@ -1216,7 +1229,9 @@ class ForwardPlan:
 
     def set_canny_thresholds(self, low, high):
         """Write the Canny thresholds the next run / replay uses (floats are floored; asynchronous on the current stream).  On a per-image
-        plan (canny="per_image") ``low`` / ``high`` are scalars (every image) or sequences of B values."""
+        plan (canny="per_image") ``low`` / ``high`` are scalars (every image) or sequences of B values.  On an automatic plan
+        (canny="auto") the same, and every image that gets a pair here becomes MANUAL (its sigma goes negative: the program leaves the pair
+        alone) until set_canny_sigma gives it a sigma again; a None entry in both sequences skips that image."""
         assert self.canny, "this plan has no Canny op (get_plan(..., canny=True))"
         from .image_ops import canny_thresholds
         if self.canny_per_image:
@@ -1224,13 +1239,30 @@ class ForwardPlan:
             if len(lows) != self.B or len(highs) != self.B:
                 raise ValueError("%d low / %d high thresholds for a batch of %d" % (len(lows), len(highs), self.B))
             for b, pair in enumerate(zip(lows, highs)):
+                if self.canny_auto and pair == (None, None):
+                    continue
                 lo, hi = canny_thresholds(*pair)
                 self.canny_thr[b, 0:1].fill_(lo)
                 self.canny_thr[b, 1:2].fill_(hi)
+                if self.canny_auto:
+                    self.canny_sigma[b:b + 1].fill_(-1)
             return
         lo, hi = canny_thresholds(low, high)
         self.canny_thr[0:1].fill_(lo)          # (fill kernels: the values travel as launch arguments, no host buffer to keep alive)
         self.canny_thr[1:2].fill_(hi)
+
+    def set_canny_sigma(self, sigma):
+        """Automatic plans (canny="auto"): write the sigma of the median rule the next run / replay uses -- one value for every image, or a
+        sequence of B values whose None entries make that image manual (it keeps the pair in canny_thr: set_canny_thresholds).  Fill
+        kernels on the current stream, as set_canny_thresholds; no re-capture."""
+        assert self.canny_auto, "this plan takes its thresholds from the host (get_plan(..., canny=\"auto\") computes them)"
+        from .image_ops import sigma_q16_list
+        vals = sigma_q16_list(sigma, self.B)
+        if len(set(vals)) == 1:
+            self.canny_sigma.fill_(vals[0])
+            return
+        for b, v in enumerate(vals):
+            self.canny_sigma[b:b + 1].fill_(v)
 
     def set_seed(self, seed, step=0):
         """Write the noise state the next run / replay starts from: ``seed`` (reduced mod 2^64) and ``step``.  Every run advances the step

@@ -19,6 +19,10 @@ the program overwrites "eps" / "noise", which a host may read back, and advances
 NUL-terminated bytes -- io names are 24 bytes, so the labels travel as data; examples/health_host.c prints them).  Per-image plans
 (--seeds S0,S1,.. / --canny-per-image LOW HIGH; ForwardPlan(rng="per_image" / canny="per_image")) have "seed" as 16 * B bytes -- one state row
 per image, i2i_randn_batch_params.states, examples/batch_host.c -- and "canny_thr" as 8 * B bytes, one {low, high} pair per image.
+Edge plans also expose "canny_edges" (uint8 [B][H][W][3], the edge map the generator saw).  Automatic-threshold plans (--canny-auto SIGMA;
+ForwardPlan(canny="auto"): the program computes "canny_thr" from the photos, i2i_canny_auto_thr_params) have "canny_sigma" (int32 [B],
+sigma * 65536, saved as given; a negative entry makes that image keep the pair the host wrote to "canny_thr") and "canny_median2" (uint32
+[B], the doubled medians of the last run): examples/auto_canny_host.c.
 Plans with per-image health (--health-per-image with --health; ForwardPlan(health_per_image=True)) have "health" as n_taps x B x 8 uint64
 (tap-major, one record per tap and image: i2i_scan_batch_params; the program zeroes them at the start of every run, so they describe the
 most recent run), "health_names" unchanged, and "verdict" (16 * B bytes: one row of four uint32 {first_bad, first_over, runs, bad_runs} per
@@ -90,6 +94,9 @@ def export_plan(plan, path, extra_tensors=(), live_scale=False):
     # plan._finish_gn_scratch; produced inside the program, zero at rest)
     if getattr(plan, "canny", False):
         named["canny_thr"] = plan.canny_thr
+        named["canny_edges"] = plan.canny_edges
+    if getattr(plan, "canny_auto", False):
+        named["canny_sigma"], named["canny_median2"] = plan.canny_sigma, plan.canny_median2
     if getattr(plan, "rng", False):
         named["seed"] = plan.rng_state
     if getattr(plan, "health", None):       # the records (zeroed in the file: a loaded plan starts counting at 0) and their labels, NUL-separated
@@ -99,8 +106,8 @@ def export_plan(plan, path, extra_tensors=(), live_scale=False):
             named["verdict"] = plan._verdict_i32
     gn_scratch = [t for t in (getattr(plan, n, None) for n in ("gn_partial", "gn_ss", "gn_counters")) if t is not None]
     if getattr(plan, "canny", False):
-        gn_scratch += [plan.canny_edges, plan.canny_ws]
-    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "seed", "health", "health_names", "verdict"), holders=[plan] + list(extra_tensors), device=plan.device,
+        gn_scratch += [plan.canny_edges, plan.canny_ws] + ([plan.canny_auto_ws] if getattr(plan, "canny_auto", False) else [])
+    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "canny_sigma", "seed", "health", "health_names", "verdict"), holders=[plan] + list(extra_tensors), device=plan.device,
                           scale_prog=scale_program_of(plan) if live_scale else None)
 
 
@@ -211,7 +218,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH]] [--seed N | --seeds S0,S1,..] [--health stages|all [--health-per-image]] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH | --canny-auto SIGMA]] [--seed N | --seeds S0,S1,..] [--health stages|all [--health-per-image]] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -237,6 +244,9 @@ def main(argv=None):
                     "seed_hi, step, 0} of image b")
     ap.add_argument("--canny-per-image", type=float, nargs=2, default=None, metavar=("LOW", "HIGH"), help="as --canny with one {low, high} pair per "
                     "image: 'canny_thr' is 8 bytes per image, every row saved as LOW HIGH")
+    ap.add_argument("--canny-auto", type=float, default=None, metavar="SIGMA", help="as --canny-per-image, with the thresholds computed by the program "
+                    "from each photo (the median rule: low = (1 - SIGMA) * median, high = (1 + SIGMA) * median; 0.33 is customary): 'canny_sigma' "
+                    "holds int32 SIGMA * 65536 per image, 'canny_thr' is written by every run")
     ap.add_argument("--health", default=None, choices=["stages", "all"], help="numerical health scans in the program (ForwardPlan(health=...)): the file "
                     "gets the buffers 'health' (8 uint64 per scanned tensor, accumulated by every run) and 'health_names' (their labels)")
     ap.add_argument("--health-per-image", action="store_true", help="with --health: one record per scanned tensor AND image ('health' holds "
@@ -254,7 +264,11 @@ def main(argv=None):
     dt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[a.dtype]
     if a.canny is not None and a.canny_per_image is not None:
         ap.error("--canny and --canny-per-image are exclusive")
-    canny_mode = "per_image" if a.canny_per_image is not None else (a.canny is not None)
+    if a.canny_auto is not None and (a.canny is not None or a.canny_per_image is not None):
+        ap.error("--canny-auto and --canny / --canny-per-image are exclusive")
+    if a.canny_auto is not None and not 0.0 <= a.canny_auto <= 1.0:
+        ap.error("--canny-auto takes a sigma in 0 .. 1")
+    canny_mode = "auto" if a.canny_auto is not None else ("per_image" if a.canny_per_image is not None else (a.canny is not None))
     if a.canny_per_image is not None:
         a.canny = a.canny_per_image
     if a.seed is not None and a.seeds is not None:
@@ -268,7 +282,7 @@ def main(argv=None):
         if len(seeds) != a.batch:
             ap.error("--seeds holds %d values for --batch %d" % (len(seeds), a.batch))
     rng_mode = "per_image" if seeds is not None else (a.seed is not None)
-    if a.canny is not None and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
+    if (a.canny is not None or a.canny_auto is not None) and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
         ap.error("--canny requires --u8 on a deterministic pix2pix plan (the edge_to_image branch; not with --sketch / --stochastic)")
     H, W = a.size[0], a.size[-1]
     if a.health_per_image and not a.health:
@@ -300,6 +314,8 @@ def main(argv=None):
         plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=canny_mode, rng=rng_mode)
         if a.canny is not None:
             plan.set_canny_thresholds(*a.canny)
+        if a.canny_auto is not None:
+            plan.set_canny_sigma(a.canny_auto)
     if seeds is not None:
         plan.set_seeds(seeds, 0)
     elif a.seed is not None:

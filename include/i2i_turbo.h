@@ -61,7 +61,8 @@ typedef enum {
     I2I_OP_CANNY_U8_BATCH = 20,
     I2I_OP_RESIZE_U8_RAGGED = 21,  /* ABI 14 addition (see the note above i2i_resize_u8_ragged_params) */
     I2I_OP_SCAN_BATCH = 22,        /* ABI 14 additions (see the note above i2i_scan_batch_params) */
-    I2I_OP_SCAN_VERDICT = 23
+    I2I_OP_SCAN_VERDICT = 23,
+    I2I_OP_CANNY_AUTO_THR = 24     /* ABI 14 addition (see the note above i2i_canny_auto_thr_params) */
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -539,6 +540,41 @@ typedef struct {
     int32_t mode;                      /* i2i_verdict_mode */
 } i2i_scan_verdict_params;
 
+/* ---- ABI 14 addition: automatic per-image Canny thresholds (I2I_OP_CANNY_AUTO_THR).  Purely additive like the ones above -- one new opcode,
+ * one new struct, two new exported functions (plus the host-side table functions i2i_resample_*); no existing struct, opcode number or
+ * signature changed and sizeof(i2i_op) did not grow -- so I2I_ABI_VERSION stays 14.  A library built before the addition is recognised by
+ * the missing symbol (i2i_canny_auto_thr), and its plan loader refuses the new opcode as unknown.
+ *
+ * The "auto-Canny" median rule, low = (1 - sigma) * median, high = (1 + sigma) * median, computed on the device from the image itself and
+ * WRITTEN into the threshold table i2i_canny_u8_batch reads, so that photo -> thresholds -> Canny -> generator is one asynchronous sequence
+ * with nothing chosen or staged by the host.  The rule is NOT part of the reference (its scripts take two hand-set numbers, defaults 100 /
+ * 200: src/inference_paired.py, gradio_canny2image.py); this comment is its contract and tests/canny_auto_ref.py the CPU oracle of it.
+ * sigma = 0.33 is the customary default of the rule, not a tuned value.  Per image b, N = h * w * c bytes, all in integers:
+ *   HISTOGRAM  256 bins over ALL bytes of the image, every channel (the np.median(image) form of the rule).
+ *   RANKS      a = the order statistic of 0-based rank (N - 1) / 2, b = the one of rank N / 2 (integer divisions);
+ *              m2 = a + b = 2 * np.median(image) exactly, 0 .. 510.
+ *   THRESHOLDS s = min(sigma_q16[b], 65536):  low = max(0, (m2 * (65536 - s)) >> 17),  high = min(255, (m2 * (65536 + s)) >> 17)
+ *              (both products fit in int32).  thr[b] = {low, high}; median2[b] = m2 if median2 is given.
+ *   MANUAL     sigma_q16[b] < 0 writes NOTHING for image b -- not thr[b], not median2[b] -- and reads none of its pixels: a request with
+ *              hand-set sliders keeps its pair in the same table, one batch mixes automatic and manual requests.
+ * Every update on the way is an integer add: the result is bit-identical for any grid and any workgroup order, and between the CPU
+ * emulator and the GPU.  No float anywhere.
+ * Three launches whose grids depend on n, h, w, c only (clear of ws; histogram: (slices of an image) x (images), capped in total, 256
+ * lanes, 16-byte loads on the aligned part of an image and byte loads on its head and tail -- an image may start at ANY byte --, one
+ * 256-bin copy per wave in LDS, one agent-scope add per non-zero bin and workgroup; select: one wave per image).  Nothing outside
+ * [0, n * N) of src is read.  No allocation, no synchronisation, no read-back; graph-capturable.  `ws` is state of the run in flight (see
+ * the CONCURRENCY note of i2i_gn_stats_params).  n == 0 is a successful no-op (checked after the sizes, before the pointers).
+ * Errors (I2I_ERR_BAD_ARG, nothing written): null params; c outside 1..4; negative n / h / w; (n > 0) an empty image (h * w == 0), N past
+ * 2^31 - 1, src / sigma_q16 / thr / ws null, thr / sigma_q16 / median2 not 4-byte aligned, ws not 16-byte aligned. */
+typedef struct {
+    const void* src;            /* uint8 [n][h][w][c], c 1..4, any byte alignment of an image start is allowed */
+    int32_t n, h, w, c;
+    const int32_t* sigma_q16;   /* device int32 [n]: sigma * 65536 per image, 0..65536; NEGATIVE = leave thr[b] untouched (manual sliders) */
+    int32_t* thr;               /* device int32 [n][2] = {low, high}: exactly i2i_canny_u8_batch_params.thr */
+    uint32_t* median2;          /* optional device uint32 [n]: the doubled median, for the caller's display; NULL = not wanted */
+    void* ws;                   /* >= i2i_canny_auto_ws_bytes(n), 16-byte aligned; contents irrelevant before and after */
+} i2i_canny_auto_thr_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -568,6 +604,7 @@ typedef struct {
         i2i_resize_u8_ragged_params resize_u8_ragged;
         i2i_scan_batch_params scan_batch;
         i2i_scan_verdict_params scan_verdict;
+        i2i_canny_auto_thr_params canny_auto_thr;
     } u;
 } i2i_op;
 
@@ -609,6 +646,8 @@ int i2i_canny_u8_batch(const i2i_canny_u8_batch_params* p, int dtype, void* stre
 int i2i_resize_u8_ragged(const i2i_resize_u8_ragged_params* p, int dtype, void* stream);   /* dtype ignored; one launch */
 int i2i_scan_batch(const i2i_scan_batch_params* p, int dtype, void* stream);           /* one launch; dtype = element type of x */
 int i2i_scan_verdict(const i2i_scan_verdict_params* p, int dtype, void* stream);       /* dtype ignored; one launch */
+int i2i_canny_auto_thr(const i2i_canny_auto_thr_params* p, int dtype, void* stream);   /* dtype ignored (uint8 data); three launches */
+size_t i2i_canny_auto_ws_bytes(int n);                                                 /* bytes of i2i_canny_auto_thr_params.ws (0 for n < 1) */
 /* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
  * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
  * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
@@ -617,6 +656,14 @@ int i2i_scan_verdict(const i2i_scan_verdict_params* p, int dtype, void* stream);
  * or I2I_ERR_BAD_ARG (null pointer, size < 1, ksize_capacity too small) with nothing written. */
 int i2i_lanczos_ksize(int in_size, int out_size);
 int i2i_lanczos_tables(int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity);
+/* The same two functions for any of Pillow's filters the resize kernels are fed with (the kernels take their taps from the tables and do not
+ * care which filter made them): I2I_FILTER_LANCZOS (support 3; what i2i_lanczos_* compute, bit for bit) and I2I_FILTER_BICUBIC (Pillow's
+ * bicubic_filter, a = -0.5, support 2: the DEFAULT of Image.resize for 8-bit images, i.e. gradio_canny2image.py:16's `input_image.resize((w8,
+ * h8))` with no filter argument).  Normalisation and the 22-bit rounding are the same; ksize = 2 * ceil(support * max(in / out, 1)) + 1.
+ * Bit-equal to image_ops.resample_coeffs(in, out, "lanczos" | "bicubic").  An unknown filter is I2I_ERR_BAD_ARG. */
+typedef enum { I2I_FILTER_LANCZOS = 0, I2I_FILTER_BICUBIC = 1 } i2i_resample_filter;
+int i2i_resample_ksize(int filter, int in_size, int out_size);
+int i2i_resample_tables(int filter, int in_size, int out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity);
 
 /* ---- grouped LoRA re-merge (ABI v13): every adapted layer of a network in ONE launch.  `create` checks the n layers as i2i_lora_merge
  * would (an error names the layer index) and uploads them as a device table with an int32 prefix array of tile counts (synchronous: setup,
@@ -655,7 +702,11 @@ int i2i_graph_destroy(void* graph);
  * "eps" (fp32 [B][4][H/8][W/8] posterior noise), "noise" (stochastic plans), "out" (images, NCHW in the plan's output dtype or uint8 NHWC);
  * plans exported with a seed also have "seed" (16 bytes: the i2i_randn_params state; the program then fills "eps" / "noise" itself;
  * 16 * B bytes, one state row per image, in a plan exported with per-image seeds: i2i_randn_batch_params.states, examples/batch_host.c);
- * edge plans have "canny_thr" (8 bytes {low, high}, or 8 * B bytes with per-image thresholds: i2i_canny_u8_batch_params.thr);
+ * edge plans have "canny_thr" (8 bytes {low, high}, or 8 * B bytes with per-image thresholds: i2i_canny_u8_batch_params.thr) and "canny_edges"
+ * (uint8 [B][H][W][3]: the edge map the generator saw, 255 on edges; the reference's saved view is 255 - it); automatic-threshold plans
+ * (i2i_canny_auto_thr_params: the program writes "canny_thr" itself) also have "canny_sigma" (4 * B bytes: int32 sigma * 65536 per image,
+ * negative = that image keeps the pair the host wrote to "canny_thr") and "canny_median2" (4 * B bytes: uint32 doubled medians of the
+ * last run): examples/auto_canny_host.c;
  * plans built with health= also have "health" (n_taps x 8 uint64: the i2i_scan_params records in program order, accumulated over the runs;
  * zero them with i2i_plan_write) and "health_names" (the n_taps labels, each NUL-terminated, as bytes): examples/health_host.c;
  * plans built with per-image health have "health" as n_taps x B x 8 uint64 (tap-major, one i2i_scan_batch_params record per tap and image,
