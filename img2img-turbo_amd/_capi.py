@@ -26,6 +26,9 @@ OP_CANNY_U8_BATCH = 20
 OP_RESIZE_U8_RAGGED = 21
 OP_SCAN_BATCH, OP_SCAN_VERDICT = 22, 23      # per-image health (i2i_scan_batch_params / i2i_scan_verdict_params)
 OP_CANNY_AUTO_THR = 24                      # automatic per-image Canny thresholds (i2i_canny_auto_thr_params)
+OP_DIGEST = 25                              # device fingerprints (i2i_digest_params)
+DIGEST_ADD, DIGEST_CLEAR = 0, 1             # i2i_digest_kind
+ERR_UNSUPPORTED, ERR_MISMATCH = -3, -5      # i2i_status values callers tell apart (i2i_plan_verify)
 FILTER_LANCZOS, FILTER_BICUBIC = 0, 1       # i2i_resample_filter
 VERDICT_CLEAR, VERDICT_JUDGE = 0, 1         # i2i_verdict_mode
 RANDN_NORMAL, RANDN_RAW, RANDN_ADVANCE = 0, 1, 2      # i2i_randn_kind
@@ -164,6 +167,11 @@ class CannyAutoThrParams(C.Structure):
     _fields_ = [("src", vp), ("n", i32), ("h", i32), ("w", i32), ("c", i32), ("sigma_q16", vp), ("thr", vp), ("median2", vp), ("ws", vp)]
 
 
+class DigestParams(C.Structure):
+    _fields_ = [("x", vp), ("images", i32), ("cols", i32), ("rows", i64), ("ld", i64), ("img_stride", i64), ("index0", C.c_uint64), ("rec", vp),
+                ("kind", i32), ("reserved", i32), ("n_records", i64)]
+
+
 class NopParams(C.Structure):
     _fields_ = [("unused", i32)]
 
@@ -175,7 +183,8 @@ class _OpUnion(C.Union):
                 ("posterior", PosteriorParams), ("ddpm", DdpmParams), ("lora_merge", LoraMergeParams), ("resize_u8", ResizeU8Params),
                 ("nop", NopParams), ("canny_u8", CannyU8Params), ("randn", RandnParams), ("twin_fold", TwinFoldParams), ("scan", ScanParams),
                 ("randn_batch", RandnBatchParams), ("canny_u8_batch", CannyU8BatchParams), ("resize_u8_ragged", ResizeU8RaggedParams),
-                ("scan_batch", ScanBatchParams), ("scan_verdict", ScanVerdictParams), ("canny_auto_thr", CannyAutoThrParams)]
+                ("scan_batch", ScanBatchParams), ("scan_verdict", ScanVerdictParams), ("canny_auto_thr", CannyAutoThrParams),
+                ("digest", DigestParams)]
 
 
 class Op(C.Structure):
@@ -187,7 +196,8 @@ _FIELD_OF = {OP_IGEMM: "igemm", OP_GN_STATS: "gn_stats", OP_GN_APPLY: "gn_apply"
              OP_NHWC_TO_NCHW: "to_nchw", OP_POSTERIOR: "posterior", OP_DDPM_POSTQUANT: "ddpm", OP_EMBED: "embed",
              OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8", OP_RANDN: "randn", OP_TWIN_FOLD: "twin_fold", OP_SCAN: "scan",
              OP_RANDN_BATCH: "randn_batch", OP_CANNY_U8_BATCH: "canny_u8_batch", OP_RESIZE_U8_RAGGED: "resize_u8_ragged",
-             OP_SCAN_BATCH: "scan_batch", OP_SCAN_VERDICT: "scan_verdict", OP_CANNY_AUTO_THR: "canny_auto_thr"}
+             OP_SCAN_BATCH: "scan_batch", OP_SCAN_VERDICT: "scan_verdict", OP_CANNY_AUTO_THR: "canny_auto_thr",
+             OP_DIGEST: "digest"}
 
 EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", "i2i_igemm", "i2i_igemm_gn_parts", "i2i_igemm_route", "i2i_gn_stats",
            "i2i_gn_apply", "i2i_nop", "i2i_calib_mfma", "i2i_calib_stream", "i2i_layernorm", "i2i_softmax", "i2i_attention", "i2i_nchw_to_nhwc",
@@ -197,7 +207,7 @@ EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", 
            "i2i_merge_group_create", "i2i_merge_group_run", "i2i_merge_group_destroy", "i2i_run", "i2i_run_timed",
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
-           "i2i_plan_has_scale", "i2i_plan_set_scale"]
+           "i2i_plan_has_scale", "i2i_plan_set_scale", "i2i_digest", "i2i_plan_verify"]
 
 
 class I2IError(RuntimeError):
@@ -250,7 +260,7 @@ class Library:
         L.i2i_sizeof_op.restype = C.c_size_t
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
                      "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
-                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr"):
+                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr", "i2i_digest"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -286,6 +296,7 @@ class Library:
         L.i2i_plan_destroy.argtypes = [vp]
         L.i2i_plan_has_scale.argtypes = [vp]
         L.i2i_plan_set_scale.argtypes = [vp, C.c_float, C.c_float, vp]
+        L.i2i_plan_verify.argtypes = [vp, vp, C.POINTER(C.c_int)]
         L.i2i_merge_group_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
         L.i2i_merge_group_run.argtypes = [vp, vp]
         L.i2i_merge_group_destroy.argtypes = [vp]
@@ -395,6 +406,13 @@ class Library:
     def plan_set_scale(self, h, r, gamma=None, stream=0):
         """New LoRA scale / skip gamma of a loaded plan exported with live_scale: enqueues its scale program on ``stream``."""
         self.check(self.lib.i2i_plan_set_scale(h, float(r), float(r if gamma is None else gamma), vp(stream)))
+
+    def plan_verify(self, h, stream=0):
+        """i2i_plan_verify of a loaded plan: (status, first_bad_buffer, message).  status 0 = every stored digest matches; ERR_MISMATCH with
+        the buffer's index; ERR_UNSUPPORTED for a file exported without digests.  Does not raise: the caller tells the three apart."""
+        bad = C.c_int(-1)
+        rc = int(self.lib.i2i_plan_verify(h, vp(stream), C.byref(bad)))
+        return rc, bad.value, ("" if rc == 0 else self.lib.i2i_last_error().decode())
 
     # ---- grouped LoRA re-merge (include/i2i_turbo.h i2i_merge_group_*) ----
     def merge_group_create(self, layers, dtype_code):

@@ -564,12 +564,175 @@ __global__ __launch_bounds__(256) void scan_verdict_judge_kernel(const uint64_t*
     }
 }
 
+// ---- i2i_digest (the contract, mixers included, is the comment of i2i_digest_params; tests/digest_ref.py restates it in numpy).  The scan's
+// shape: grid (slices of an image, images), a workgroup works on one image at a time, per image the 16-byte chunks of its x slice
+// (SCAN_UNROLL loads in flight per lane) and then the head / tail elements one per lane.  Elements are told apart by their size only (the
+// value is the bit pattern): fp16 and bf16 share a kernel.
+// Cost per element: the Weyl step g = j * DIGEST_W is ONE 64-bit multiply per chunk (or edge element) and a 64-bit add per further element
+// of the chunk; what stays per element is three 64-bit multiplies by constants -- hipcc lowers each to one v_mad_u64_u32 and two
+// v_mul_lo_u32, nine quarter-rate instructions per element -- plus about twenty shifts, xors and adds: the kernel is bound by the integer
+// multiplies, not by the bytes it reads (DESIGN.md has the measured rates).
+constexpr int DIGEST_MAX_GRID = 1024;          // workgroups of one launch at most, split as SCAN_BATCH_MAX_GRID is
+constexpr uint64_t DIGEST_W = 0x9E3779B97F4A7C15ull, DIGEST_K1 = 0xFF51AFD7ED558CCDull, DIGEST_K2 = 0xC4CEB9FE1A85EC53ull,
+                   DIGEST_K3 = 0xD6E8FEB86659FD93ull;
+
+struct DigestArgs {
+    const char* x; int32_t images; int64_t rows, cols, ld, img_stride;       // (a contiguous image arrives as ONE row of rows * cols elements)
+    uint64_t n_elems, index0; uint64_t* rec;
+};
+struct DigestAcc { uint64_t s0, s1; };
+
+// g = (index0 + p) * DIGEST_W of the element, v its zero-extended bit pattern
+__device__ __forceinline__ void digest_elem(uint64_t g, uint32_t v, DigestAcc& c) {
+    uint64_t m = g ^ (uint64_t)v;
+    m ^= m >> 33;
+    m *= DIGEST_K1;
+    m ^= m >> 33;
+    m *= DIGEST_K2;
+    m ^= m >> 33;
+    c.s0 += m;
+    const uint64_t t = (m ^ (m >> 31)) * DIGEST_K3;
+    c.s1 += t ^ (t >> 32);
+}
+
+// the 16 / ESZ elements of one chunk, in memory order; g0 belongs to the first
+template <int ESZ> __device__ __forceinline__ void digest_chunk(const u32x4 v, uint64_t g0, DigestAcc& c) {
+    constexpr int PER = 4 / ESZ;                 // elements per 32-bit word (little endian: the lowest bits come first)
+    constexpr uint32_t MASK = ESZ == 4 ? 0xFFFFFFFFu : ((1u << (8 * (ESZ & 3))) - 1u);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+#pragma unroll
+        for (int e = 0; e < PER; ++e) {
+            digest_elem(g0, ESZ == 4 ? v[w] : ((v[w] >> (8 * ESZ * e)) & MASK), c);
+            g0 += DIGEST_W;
+        }
+    }
+}
+
+template <int ESZ, bool ONE_ROW>
+__global__ __launch_bounds__(SCAN_THREADS) void digest_kernel(const DigestArgs a) {
+    constexpr int EPC = 16 / ESZ;
+    typedef typename std::conditional<ESZ == 4, uint32_t, typename std::conditional<ESZ == 2, uint16_t, uint8_t>::type>::type word_t;
+    uint64_t* red = (uint64_t*)i2i_smem;          // [waves][2]
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int b = (int)blockIdx.y; b < a.images; b += (int)gridDim.y) {
+        const char* x = a.x + (int64_t)b * a.img_stride * ESZ;
+        // this image's split, from ITS start address (as scan_batch_kernel): elements in front of the first 16-byte boundary, chunks, the rest
+        const int64_t mis = (int64_t)(((uintptr_t)x & 15) / ESZ);
+        int64_t head, nb, tail;
+        if (ONE_ROW) {
+            head = mis ? (EPC - mis < a.cols ? EPC - mis : a.cols) : 0;
+            nb = (a.cols - head) / EPC, tail = a.cols - head - nb * EPC;
+        } else if (mis == 0 && a.ld % EPC == 0) {
+            head = 0, nb = a.cols / EPC, tail = a.cols % EPC;                // every row of this image starts on a 16-byte boundary
+        } else {
+            head = 0, nb = 0, tail = a.cols;                                 // element loads throughout
+        }
+        DigestAcc c = {0u, 0u};
+        const int64_t step = (int64_t)gridDim.x * (SCAN_THREADS * SCAN_UNROLL);
+        const int64_t items = a.rows * nb;
+        const char* body = x + head * ESZ;
+        auto chunk_at = [&](int64_t i) -> const u32x4* {
+            if (ONE_ROW) return (const u32x4*)body + i;
+            const int64_t row = i / nb, j = i - row * nb;
+            return (const u32x4*)(body + row * a.ld * ESZ) + j;
+        };
+        auto g_of_chunk = [&](int64_t i) -> uint64_t {          // (index0 + element number of the chunk's first element) * W
+            if (ONE_ROW) return (a.index0 + (uint64_t)(head + i * EPC)) * DIGEST_W;
+            const int64_t row = i / nb, j = i - row * nb;
+            return (a.index0 + (uint64_t)(row * a.cols + j * EPC)) * DIGEST_W;
+        };
+        int64_t i0 = (int64_t)blockIdx.x * (SCAN_THREADS * SCAN_UNROLL) + threadIdx.x;
+        for (; i0 + (SCAN_UNROLL - 1) * SCAN_THREADS < items; i0 += step) {
+            u32x4 v[SCAN_UNROLL];
+#pragma unroll
+            for (int u = 0; u < SCAN_UNROLL; ++u) v[u] = *chunk_at(i0 + u * SCAN_THREADS);
+            scan_fence(v);      // all loads of the round are issued before the first is consumed
+#pragma unroll
+            for (int u = 0; u < SCAN_UNROLL; ++u) digest_chunk<ESZ>(v[u], g_of_chunk(i0 + u * SCAN_THREADS), c);
+        }
+        if (i0 < items) {               // the last, partial round of this lane
+            for (int u = 0; u < SCAN_UNROLL - 1; ++u) {
+                const int64_t i = i0 + u * SCAN_THREADS;
+                if (i < items) digest_chunk<ESZ>(*chunk_at(i), g_of_chunk(i), c);
+            }
+        }
+        const int64_t edge = head + tail, n_edge = a.rows * edge;
+        for (int64_t i = (int64_t)blockIdx.x * SCAN_THREADS + threadIdx.x; i < n_edge; i += (int64_t)gridDim.x * SCAN_THREADS) {
+            const int64_t row = ONE_ROW ? 0 : i / edge, e = i - row * edge;
+            const int64_t col = e < head ? e : e + nb * EPC;
+            digest_elem((a.index0 + (uint64_t)(row * a.cols + col)) * DIGEST_W, (uint32_t)((const word_t*)x)[row * a.ld + col], c);
+        }
+        // lanes -> wave -> workgroup through LDS -> one add per sum, workgroup and image
+        const uint64_t w0 = wave_sum_u64(c.s0), w1 = wave_sum_u64(c.s1);
+        if (lane == 0) red[wave * 2 + 0] = w0, red[wave * 2 + 1] = w1;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t* rec = a.rec + (int64_t)b * 4;
+            uint64_t t0 = 0, t1 = 0;
+            for (int w = 0; w < SCAN_THREADS / 64; ++w) t0 += red[w * 2 + 0], t1 += red[w * 2 + 1];
+            agent_add_u64(rec + 0, t0);
+            agent_add_u64(rec + 1, t1);
+            if (blockIdx.x == 0) agent_add_u64(rec + 2, a.n_elems);       // exactly one lane of the launch per image
+        }
+        __syncthreads();                              // `red` is free again before the next image of this workgroup fills it
+    }
+}
+
+template <int ESZ> int digest_launch(const i2i_digest_params& p, hipStream_t s) {
+    constexpr int64_t EPC = 16 / ESZ;
+    DigestArgs a;
+    a.x = (const char*)p.x, a.images = p.images, a.img_stride = p.img_stride;
+    a.n_elems = (uint64_t)p.rows * (uint64_t)p.cols, a.index0 = p.index0, a.rec = p.rec;
+    a.rows = p.rows, a.cols = p.cols, a.ld = p.ld;
+    if (p.ld == p.cols || p.rows <= 1) a.cols = (int64_t)a.n_elems, a.rows = 1, a.ld = a.cols;      // contiguous images: one long row each
+    // slices per image and the cap on the whole grid: scan_batch_launch's rule
+    const int64_t per = SCAN_THREADS * SCAN_UNROLL;
+    const bool chunks = a.rows == 1 || a.ld % EPC == 0;
+    const int64_t work = chunks ? a.rows * ((a.cols + EPC - 1) / EPC) : a.rows * a.cols, want = (work + per - 1) / per;
+    const unsigned gy = (unsigned)(p.images < DIGEST_MAX_GRID ? p.images : DIGEST_MAX_GRID);
+    const int64_t cap = DIGEST_MAX_GRID / gy;
+    const unsigned gx = (unsigned)(want < 1 ? 1 : (want > cap ? cap : want));
+    const size_t smem = (SCAN_THREADS / 64) * 2 * sizeof(uint64_t);
+    if (a.rows == 1) hipLaunchKernelGGL((digest_kernel<ESZ, true>), dim3(gx, gy), dim3(SCAN_THREADS), smem, s, a);
+    else hipLaunchKernelGGL((digest_kernel<ESZ, false>), dim3(gx, gy), dim3(SCAN_THREADS), smem, s, a);
+    return i2i::check_launch("digest");
+}
+
 inline unsigned grid_for(int64_t n) {
     const int64_t b = (n + 255) / 256;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
 }  // namespace
+
+extern "C" int i2i_digest(const i2i_digest_params* p, int dtype, void* stream) {
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "digest: null params");
+    hipStream_t s = (hipStream_t)stream;
+    if (p->kind == I2I_DIGEST_CLEAR) {
+        if (!p->rec || ((uintptr_t)p->rec & 7)) return i2i::fail(I2I_ERR_BAD_ARG, "digest: rec is null or not 8-byte aligned");
+        if (p->n_records < 0 || p->n_records > ((int64_t)1 << 40)) return i2i::fail(I2I_ERR_BAD_ARG, "digest: n_records = %lld", (long long)p->n_records);
+        if (p->n_records == 0) return I2I_OK;
+        hipLaunchKernelGGL(scan_verdict_clear_kernel, dim3(grid_for(p->n_records * 4)), dim3(256), 0, s, p->rec, p->n_records * 4);
+        return i2i::check_launch("digest_clear");
+    }
+    if (p->kind != I2I_DIGEST_ADD) return i2i::fail(I2I_ERR_BAD_ARG, "digest: unknown kind %d", p->kind);
+    const int esz = dtype == I2I_F32 ? 4 : (dtype == I2I_BF16 || dtype == I2I_F16) ? 2 : dtype == I2I_U8 ? 1 : 0;
+    if (!esz) return i2i::fail(I2I_ERR_BAD_ARG, "digest: dtype %d is not one of u8 / f16 / bf16 / f32", dtype);
+    if (p->images < 0) return i2i::fail(I2I_ERR_BAD_ARG, "digest: images = %d < 0", p->images);
+    if (p->rows < 0 || p->cols < 0 || p->ld < p->cols)
+        return i2i::fail(I2I_ERR_BAD_ARG, "digest: rows = %lld, cols = %d, ld = %lld", (long long)p->rows, p->cols, (long long)p->ld);
+    const int64_t big = (int64_t)1 << 61;
+    if (p->rows > 0 && p->ld > big / p->rows) return i2i::fail(I2I_ERR_BAD_ARG, "digest: rows * ld = %lld * %lld is too large", (long long)p->rows, (long long)p->ld);
+    const int64_t extent = p->rows > 0 ? (p->rows - 1) * p->ld + p->cols : 0;      // elements from an image's first to behind its last
+    if (p->images > 0 && (p->img_stride < extent || p->img_stride > big / p->images))
+        return i2i::fail(I2I_ERR_BAD_ARG, "digest: img_stride = %lld (an image spans %lld elements, %d images)", (long long)p->img_stride, (long long)extent, p->images);
+    if (p->images == 0 || p->rows == 0 || p->cols == 0) return I2I_OK;
+    if (!p->x || !p->rec) return i2i::fail(I2I_ERR_BAD_ARG, "digest: null pointer");
+    if ((uintptr_t)p->x % (uintptr_t)esz) return i2i::fail(I2I_ERR_BAD_ARG, "digest: x is not aligned to its element type");
+    if ((uintptr_t)p->rec & 7) return i2i::fail(I2I_ERR_BAD_ARG, "digest: rec is not 8-byte aligned");
+    return esz == 4 ? digest_launch<4>(*p, s) : esz == 2 ? digest_launch<2>(*p, s) : digest_launch<1>(*p, s);
+}
 
 extern "C" int i2i_nchw_to_nhwc(const i2i_nchw_to_nhwc_params* p, int dtype, void* stream) {
     if (!p || !p->x || !p->y || p->cpad < p->c) return i2i::fail(I2I_ERR_BAD_ARG, "nchw_to_nhwc: bad args");

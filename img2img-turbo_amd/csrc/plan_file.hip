@@ -19,12 +19,19 @@
 //   relocs   : n_relocs x { u32 op; u32 field_offset (bytes inside i2i_op); u32 buf; u32 pad; u64 offset }   -> *(void**)(op + field_offset) = base[buf] + offset
 //   ops      : (n_ops + n_scale_ops) x sizeof(i2i_op) bytes (pointer fields are meaningless until patched; non-pointer fields verbatim)
 //   data     : the contents of every kind-1 buffer, in buffer order
+//   digests  : OPTIONAL, behind the data (exported with digests): "I2IDIGS1", u32 count, u32 pad, count x { u32 buf; u32 pad; u64 s0, s1, elements }
+//              -- the i2i_digest_params record of the whole buffer as bytes (I2I_U8, index0 = 0) for every kind-1 buffer that no op writes and
+//              no io name exposes (weights, constants, tables); i2i_plan_verify computes them again on the device.  A file without the section
+//              ends with the data, as every file did before the section existed.
 //
 // What the loader checks (a plan file is an EXECUTABLE artefact -- it names kernels, shapes and strides -- so it deserves the trust of the
 // library itself; the checks below keep a damaged or stale file from becoming a wild write, they do not make a hostile one safe):
 // table sizes, every io / relocation record inside its buffer (overflow-safe), a relocation may only patch a field that IS a pointer
 // of that op's parameter struct (ptr_fields below), and every pointer field must be null in the file -- relocations are the only
 // source of addresses, an exporter-process address can never be used.  Allocation failures and exceptions are reported as errors.
+// The digest section: whatever follows the data must be exactly one well-formed section -- magic, a count no larger than the buffer table,
+// `count` whole records and then the end of the file; every record names a kind-1 buffer, none twice, and its element count is that
+// buffer's size.  Anything else fails the load.
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -52,6 +59,7 @@ struct BufRec { uint64_t bytes; uint32_t kind, pad; };
 struct IoRec { char name[24]; uint32_t buf, pad; uint64_t offset, bytes; };
 struct RelocRec { uint32_t op, field_offset, buf, pad; uint64_t offset; };
 struct Header { char magic[8]; uint32_t abi, sizeof_op, n_ops, n_bufs, n_relocs, n_io; };
+struct DigestRec { uint32_t buf, pad; uint64_t s0, s1, elements; };
 
 struct Plan {
     std::vector<void*> base;
@@ -63,6 +71,8 @@ struct Plan {
     std::vector<void*> groups;                // the plain merges of the scale program, one i2i_merge_group per dtype
     std::vector<i2i_op> scale_rest;           // what runs per op after the groups: LayerNorm-fold merges, the TwinConv fold
     std::vector<float*> rgs;                  // every distinct device (r, gamma) pair the plan reads
+    bool has_digests = false;
+    std::vector<DigestRec> digests;           // the file's digest section (i2i_plan_verify)
     ~Plan() {
         for (void* g : groups) i2i_merge_group_destroy(g);
         for (void* p : base) if (p) i2i::rt_free(p);
@@ -105,7 +115,9 @@ const std::vector<size_t>& ptr_fields(int opcode) {
     static const std::vector<size_t> scan_verdict = {PF(scan_verdict, rec), PF(scan_verdict, verdict)};
     static const std::vector<size_t> canny_auto = {PF(canny_auto_thr, src), PF(canny_auto_thr, sigma_q16), PF(canny_auto_thr, thr),
                                                    PF(canny_auto_thr, median2), PF(canny_auto_thr, ws)};
+    static const std::vector<size_t> digest = {PF(digest, x), PF(digest, rec)};
     switch (opcode) {
+        case I2I_OP_DIGEST: return digest;
         case I2I_OP_CANNY_AUTO_THR: return canny_auto;
         case I2I_OP_SCAN_BATCH: return scan_batch;
         case I2I_OP_SCAN_VERDICT: return scan_verdict;
@@ -225,6 +237,29 @@ static int plan_load_impl(const char* path, void** plan_out) {
             left -= n;
         }
     }
+    // the optional digest section: nothing, or exactly one well-formed section up to the end of the file
+    {
+        char magic[8];
+        const size_t got = fread(magic, 1, sizeof(magic), f);
+        if (got != 0) {
+            uint32_t cnt[2];
+            if (got != sizeof(magic) || memcmp(magic, "I2IDIGS1", 8) != 0) return bail(I2I_ERR_BAD_ARG, "bytes behind the data section that are not a digest section");
+            if (!read_exact(f, cnt, sizeof(cnt))) return bail(I2I_ERR_BAD_ARG, "truncated digest section");
+            if (cnt[0] > h.n_bufs) return bail(I2I_ERR_BAD_ARG, "the digest section counts more records than the file has buffers");
+            pl->digests.resize(cnt[0]);
+            if (!read_exact(f, pl->digests.data(), (size_t)cnt[0] * sizeof(DigestRec))) return bail(I2I_ERR_BAD_ARG, "truncated digest section");
+            char extra;
+            if (fread(&extra, 1, 1, f) != 0) return bail(I2I_ERR_BAD_ARG, "bytes behind the digest section");
+            std::vector<bool> seen(h.n_bufs, false);
+            for (const DigestRec& d : pl->digests) {
+                if (d.buf >= h.n_bufs) return bail(I2I_ERR_BAD_ARG, "a digest record names a buffer the file does not have");
+                if (pl->bufs[d.buf].kind != 1 || seen[d.buf]) return bail(I2I_ERR_BAD_ARG, "a digest record names a scratch buffer, or a buffer twice");
+                if (d.elements != pl->bufs[d.buf].bytes) return bail(I2I_ERR_BAD_ARG, "a digest record does not cover its whole buffer");
+                seen[d.buf] = true;
+            }
+            pl->has_digests = true;
+        }
+    }
     for (const RelocRec& r : rel) {
         void* v = (char*)pl->base[r.buf] + r.offset;
         memcpy((char*)&pl->ops[r.op] + r.field_offset, &v, sizeof(void*));
@@ -330,6 +365,49 @@ extern "C" int i2i_plan_set_scale(void* plan, float r, float gamma, void* stream
         if (rc != I2I_OK) return rc;
     }
     return i2i_run(pl->scale_rest.data(), (int)pl->scale_rest.size(), stream);
+}
+
+extern "C" int i2i_plan_verify(void* plan, void* stream, int* first_bad_buffer) {
+    if (!plan) return i2i::fail(I2I_ERR_BAD_ARG, "plan_verify: null plan");
+    const Plan* pl = (const Plan*)plan;
+    if (first_bad_buffer) *first_bad_buffer = -1;
+    if (!pl->has_digests)
+        return i2i::fail(I2I_ERR_UNSUPPORTED, "plan_verify: this plan file carries no digests: export it with digests (plan_file.py --digests)");
+    const size_t n = pl->digests.size();
+    if (n == 0) return I2I_OK;
+    struct Dev { void* p; ~Dev() { if (p) i2i::rt_free(p); } } rec{i2i::rt_alloc(n * 32)};
+    if (!rec.p) return i2i::fail(I2I_ERR_RUNTIME, "plan_verify: out of device memory");
+    if (i2i::rt_zero(rec.p, n * 32) != I2I_OK || i2i::rt_sync() != I2I_OK) return i2i::fail(I2I_ERR_RUNTIME, "plan_verify: memset failed");
+    const uint64_t piece = (uint64_t)1 << 30;          // cols is an int32: a large buffer goes in pieces (digest(A || B) = digest(A) + digest(B, index0 = len A))
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t bytes = pl->bufs[pl->digests[i].buf].bytes;
+        for (uint64_t at = 0; at < bytes; at += piece) {
+            i2i_digest_params p;
+            memset(&p, 0, sizeof(p));
+            p.x = (const char*)pl->base[pl->digests[i].buf] + at;
+            p.images = 1, p.rows = 1, p.cols = (int32_t)(bytes - at < piece ? bytes - at : piece), p.ld = p.cols, p.img_stride = p.cols;
+            p.index0 = at, p.rec = (uint64_t*)rec.p + 4 * i, p.kind = I2I_DIGEST_ADD;
+            const int rc = i2i_digest(&p, I2I_U8, stream);
+            if (rc != I2I_OK) return rc;
+        }
+    }
+    if (i2i::rt_sync() != I2I_OK) return i2i::fail(I2I_ERR_RUNTIME, "plan_verify: device synchronisation failed");
+    try {
+        std::vector<uint64_t> got(n * 4);
+        if (i2i::rt_download(got.data(), rec.p, n * 32) != I2I_OK) return i2i::fail(I2I_ERR_RUNTIME, "plan_verify: download failed");
+        for (size_t i = 0; i < n; ++i) {
+            const DigestRec& d = pl->digests[i];
+            if (got[4 * i] != d.s0 || got[4 * i + 1] != d.s1 || got[4 * i + 2] != d.elements) {
+                if (first_bad_buffer) *first_bad_buffer = (int)d.buf;
+                return i2i::fail(I2I_ERR_MISMATCH, "plan_verify: buffer %u (%llu bytes) differs from the file's digest: stored %016llx %016llx, computed %016llx %016llx",
+                                 d.buf, (unsigned long long)d.elements, (unsigned long long)d.s0, (unsigned long long)d.s1,
+                                 (unsigned long long)got[4 * i], (unsigned long long)got[4 * i + 1]);
+            }
+        }
+    } catch (const std::exception& e) {
+        return i2i::fail(I2I_ERR_RUNTIME, "plan_verify: %s", e.what());
+    }
+    return I2I_OK;
 }
 
 extern "C" int i2i_plan_destroy(void* plan) {

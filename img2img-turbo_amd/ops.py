@@ -251,6 +251,25 @@ def scan_verdict(rec, verdict, *, taps, images, mode):
     return K.OP_SCAN_VERDICT, _keep(p, rec, verdict)
 
 
+def digest(x, rec, *, images, rows, cols, ld=None, img_stride=None, index0=0):
+    """rec[b][0..3] (an int64 tensor holding uint64 bits, 32 bytes per image) += the fingerprint {s0, s1, elements, 0} of image b's rows x cols
+    view of ``x`` (the contract: i2i_digest_params, include/i2i_turbo.h).  The op's dtype must be the element type of ``x`` (K.U8 for bytes)."""
+    p = K.DigestParams()
+    p.x, p.rec = ptr(x), ptr(rec)
+    ld = int(cols if ld is None else ld)
+    p.images, p.rows, p.cols, p.ld = int(images), int(rows), int(cols), ld
+    p.img_stride = int(int(rows) * ld if img_stride is None else img_stride)
+    p.index0, p.kind = int(index0) & (2 ** 64 - 1), K.DIGEST_ADD
+    return K.OP_DIGEST, _keep(p, x, rec)
+
+
+def digest_clear(rec, *, n_records):
+    """Zero ``n_records`` 32-byte fingerprint records from ``rec`` on (I2I_DIGEST_CLEAR)."""
+    p = K.DigestParams()
+    p.rec, p.kind, p.n_records = ptr(rec), K.DIGEST_CLEAR, int(n_records)
+    return K.OP_DIGEST, _keep(p, rec)
+
+
 def nhwc_to_nchw(x, y, *, n, c, h, w, ldx, clamp=0, mul=0.0, add=0.0):
     """y: NCHW float tensor, or a uint8 HWC image batch [n, h, w, c] (then y = trunc(clamp01(x*mul+add)*255))."""
     p = K.NhwcToNchwParams()

@@ -67,7 +67,7 @@ class TurboGeneratorBase(torch.nn.Module):
 
     def __init__(self, weights: GeneratorWeights, device="cuda", dtype=torch.float32, lib=None,
                  tokenizer=None, text_encoder=None, use_graph=True, fuse_gn=True, flash=True, plan_options=None, unet_dtype=None, live_scale=False,
-                 health=None, health_limit=None, health_per_image=False):
+                 health=None, health_limit=None, health_per_image=False, fingerprint=None):
         """``dtype``: element type of activations and packed weights (fp32 = the exact-MFMA parity mode).  ``unet_dtype``: another 16-bit
         type for the UNet alone -- ``dtype=torch.bfloat16, unet_dtype=torch.float16`` keeps the VAE (whose real activations overflow fp16)
         in bf16 and gives the UNet, whose error the 1-step scheduler multiplies by 14.6, fp16's three extra mantissa bits.
@@ -81,8 +81,13 @@ class TurboGeneratorBase(torch.nn.Module):
         ``health_limit``: the near-saturation threshold (default: half the largest finite value of each scanned tensor's dtype).
         ``health_per_image=True`` (with ``health=``): one record per tap AND IMAGE and a per-image verdict computed by the program itself
         (ForwardPlan(health_per_image=True), the contracts of i2i_scan_batch_params / i2i_scan_verdict_params): ``health_verdict()`` says which
-        request of the batch went non-finite and at which tap; the records then describe the most recent run alone."""
+        request of the batch went non-finite and at which tap; the records then describe the most recent run alone.
+        ``fingerprint="io"`` / ``"stages"`` / ``"all"``: every plan carries device fingerprints (ForwardPlan(fingerprint=...), the contract of
+        i2i_digest_params) -- one 128-bit digest per tap and image of the most recent run, read with ``fingerprint()``; two runs, two GPUs or
+        two hosts that computed the same bits have equal lists, and ``digest.first_diff`` names the first tap and request that differ."""
         super().__init__()
+        assert fingerprint in (None, "io", "stages", "all"), fingerprint
+        self.fingerprint_mode = fingerprint
         assert health in (None, "stages", "all"), health
         assert health or not health_per_image, "health_per_image needs health=\"stages\" or \"all\""
         self.health, self.health_limit, self.health_per_image = health, health_limit, bool(health_per_image)
@@ -166,6 +171,30 @@ class TurboGeneratorBase(torch.nn.Module):
         """Zero the records (and the per-image verdict rows) of the most recently run plan (asynchronous on the current stream)."""
         self._health_plan().health_reset()
 
+    # ---- device fingerprints ----
+    def fingerprint(self):
+        """[(label, uint64 [B, 4])] of the most recently run plan, in program order (ForwardPlan.fingerprint; synchronises)."""
+        if not self.fingerprint_mode:
+            raise _capi.I2IError("fingerprints are off: construct the model with fingerprint=\"io\", \"stages\" or \"all\"")
+        if self._last_plan is None or self._last_plan.released:
+            raise _capi.I2IError("no forward has run yet (or its plan was released)")
+        return self._last_plan.fingerprint()
+
+    def weights_fingerprint(self):
+        """(records, total): one (label, uint64 [4]) per packed weight buffer of every packer built so far -- the buffers the kernels read,
+        with the LoRA merged at the current scale -- in packing order, and their field-wise sum mod 2^64.  Computed on the device that holds
+        them (digest.digest, on the current stream: ordered behind a set_lora_scale); reads back 32 bytes per buffer."""
+        from .digest import digest
+        records, total = [], torch.zeros(4, dtype=torch.int64)
+        with self._on_device():
+            for (dt, which), pk in self._packers.items():
+                for key, ent in pk.cache.items():
+                    if isinstance(ent, dict) and isinstance(ent.get("w"), torch.Tensor):
+                        rec = digest(ent["w"], lib=self.lib)[0]
+                        records.append(("%s[%s]:%s" % (which, str(dt).replace("torch.", ""), "/".join(str(k) for k in (key if isinstance(key, tuple) else (key,)))), rec))
+                        total += rec.view(torch.int64)          # (int64 adds wrap like uint64 ones)
+        return records, total.view(torch.uint64)
+
     # ---- plumbing ----
     def _on_device(self):
         import contextlib
@@ -218,7 +247,8 @@ class TurboGeneratorBase(torch.nn.Module):
         key = ((B, H, W, self.dtype_, self.unet_dtype_, stochastic, direction, ctx_batch, u8_io)
                + ((("canny_per_image",) if canny == "per_image" else (("canny_auto",) if canny == "auto" else (True,))) if canny else ())
                + ((("rng_per_image",) if rng == "per_image" else ("rng",)) if rng else ())
-               + (("health", self.health, self.health_limit) if self.health else ()) + (("health_per_image",) if self.health_per_image else ()))
+               + (("health", self.health, self.health_limit) if self.health else ()) + (("health_per_image",) if self.health_per_image else ())
+               + (("fingerprint", self.fingerprint_mode) if self.fingerprint_mode else ()))
         if key in self._plans:
             self._plans.move_to_end(key)
         else:
@@ -233,6 +263,8 @@ class TurboGeneratorBase(torch.nn.Module):
                 opts["health"], opts["health_limit"] = self.health, self.health_limit
                 if self.health_per_image:
                     opts["health_per_image"] = True
+            if self.fingerprint_mode:
+                opts["fingerprint"] = self.fingerprint_mode
             with self._on_device():
                 self._plans[key] = ForwardPlan(self.lib, self.weights, B, H, W, self.dtype_, self.device_, stochastic=stochastic,
                                                r=self._r, direction=direction, ctx_batch=ctx_batch, fuse_gn=self.fuse_gn,

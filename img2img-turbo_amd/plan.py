@@ -86,7 +86,7 @@ class ForwardPlan:
 
     def __init__(self, lib, weights, B, H, W, dtype, device, *, stochastic=False, r=1.0, direction="a2b",
                  ctx_batch=1, fuse_gn=True, flash=True, out_dtype=None, packers=None, debug=False, dma_small=True, fuse_gn_stats=True, subpix=True, halo_min_tiles=160, u8_io=None, fuse_vae_attention=True,
-                 unet_dtype=None, canny=False, rng=False, health=None, health_limit=None, health_per_image=False):
+                 unet_dtype=None, canny=False, rng=False, health=None, health_limit=None, health_per_image=False, fingerprint=None):
         assert H % 8 == 0 and W % 8 == 0, "input must be a multiple of 8 (src/inference_paired.py:38-41)"
         # H, W multiples of 8 suffice (src/inference_paired.py:38-41): latent sizes that are not multiples of 8 make the
         # UNet levels odd (70 -> 35 -> 18 -> 9), handled like diffusers' forward_upsample_size path (explicit sizes).
@@ -133,6 +133,16 @@ class ForwardPlan:
         self.health_verdict_rows = None
         self.health_labels, self.health_taps, self.health_rec = [], [], None      # health_taps[i] = (tensor, rows, cols, ld) of record i
         self._health_ops = []
+        # fingerprint: None | "io" | "stages" | "all" -- device fingerprints (I2I_OP_DIGEST, the contract of i2i_digest_params in
+        # include/i2i_turbo.h): "stages" / "all" digest the same tensors, at the same places of the program, as health= scans them, always ONE
+        # RECORD PER IMAGE (every tap is batch-outermost); "io" digests the boundary buffers alone, behind the last op -- x, the ctx / eps /
+        # noise the program read (a shared context, ctx_batch = 1, lands in image 0's record; the others of that tap stay zero) and out.
+        # `fingerprint_rec` is uint64 [n_taps][B][4] = {s0, s1, elements, 0}, tap-major; the program starts with one CLEAR of it
+        # (I2I_DIGEST_CLEAR, beside the health CLEAR), so after any run or graph replay the records describe THAT run.  Off (the default)
+        # the program, its op count and its buffers are what they were.
+        assert fingerprint in (None, "io", "stages", "all"), fingerprint
+        self.fingerprint_mode = fingerprint
+        self.fingerprint_labels, self.fingerprint_rec, self._fp_ops, self._fp_clear = [], None, [], None
         self.prog = K.Program()
         self.op_flops = []      # algorithmic FLOPs per op (2*MAC), parallel to prog.ops
         self.op_flops_exec = [] # FLOPs the matrix pipe executes for the op (sub-pixel upsamplers: 4/9 of the 3x3 part), parallel to prog.ops
@@ -224,11 +234,22 @@ class ForwardPlan:
             self._verdict_ops = [O.scan_verdict(None, None, taps=0, images=B, mode=K.VERDICT_CLEAR),
                                  O.scan_verdict(None, None, taps=0, images=B, mode=K.VERDICT_JUDGE)]
             self._add(self._verdict_ops[0], "health: clear", kernel="scan_verdict")
+        if self.fingerprint_mode:
+            self._fp_clear = O.digest_clear(None, n_records=0)
+            self._add(self._fp_clear, "fingerprint: clear", kernel="digest_clear")
         self._build()
+        if self.fingerprint_mode == "io":
+            self._fp("x", self.x_in, B, self.x_in.numel() // B)
+            self._fp("ctx", self.ctx, ctx_batch, self.ctx.numel() // ctx_batch, images=ctx_batch)
+            self._fp("eps", self.eps, B, self.eps.numel() // B)
+            if self.noise is not None:
+                self._fp("noise", self.noise, B, self.noise.numel() // B)
+            self._fp("out", self.out, B, self.out.numel() // B)
         if self.health_per_image:
             self._add(self._verdict_ops[1], "health: verdict", kernel="scan_verdict")
         self._finish_gn_scratch()
         self._finish_health()
+        self._finish_fingerprint()
         self.prog.freeze()
         self.graph = None
 
@@ -284,18 +305,21 @@ class ForwardPlan:
         self.health_taps.append((t, rows, cols, cols if ld is None else ld))
 
     def _tap(self, label, a: Act, cols=None):
-        """A tensor registered in `taps` (health="all")."""
+        """A tensor registered in `taps` (health="all" / fingerprint="all")."""
         if self.health == "all":
             self._scan(label, a.t, a.n * a.hw, cols or a.c, a.c)
+        if self.fingerprint_mode == "all":
+            self._fp(label, a.t, a.n * a.hw, cols or a.c, a.c)
 
     def _stage(self, label, a, cols=None, rows=None):
         """A stage boundary (both modes).  ``a``: an Act, or a flat tensor with ``rows`` / ``cols``."""
-        if self.health is None:
-            return
-        if isinstance(a, Act):
-            self._scan(label, a.t, a.n * a.hw, cols or a.c, a.c)
-        else:
-            self._scan(label, a, rows, cols)
+        for on, record in ((self.health is not None, self._scan), (self.fingerprint_mode in ("stages", "all"), self._fp)):
+            if not on:
+                continue
+            if isinstance(a, Act):
+                record(label, a.t, a.n * a.hw, cols or a.c, a.c)
+            else:
+                record(label, a, rows, cols)
 
     def _finish_health(self):
         if self.health is None:
@@ -316,6 +340,45 @@ class ForwardPlan:
                 p.rec, p.verdict, p.taps = self._health_i64.data_ptr(), self._verdict_i32.data_ptr(), n
                 p._keep = (self._health_i64, self._verdict_i32)
         self.health_names = torch.tensor(list(b"".join(l.encode() + b"\0" for l in self.health_labels)) or [0], dtype=torch.uint8, device=self.device)
+
+    # ------------------------------------------------------------------ device fingerprints
+    def _fp(self, label, t, rows, cols, ld=None, images=None):
+        """Record one digest of the rows x cols view of tensor ``t`` (batch-outermost: image b is rows / images consecutive rows), one record
+        per image; the record pointer is patched in _finish_fingerprint."""
+        from .digest import dtype_code
+        images = self.B if images is None else images
+        assert rows % images == 0, "tap %s is not batch-outermost: %d rows for %d images" % (label, rows, images)
+        op = O.digest(t, None, images=images, rows=rows // images, cols=cols, ld=ld)
+        old = self.dt
+        self.dt = dtype_code(t)          # (uint8 boundary buffers included: not a type an activation op can have)
+        try:
+            self._add(op, "fingerprint: " + label, kernel="digest_kernel", nbytes=rows * cols * t.element_size())
+        finally:
+            self.dt = old
+        self._fp_ops.append(op[1])
+        self.fingerprint_labels.append(label)
+
+    def _finish_fingerprint(self):
+        if not self.fingerprint_mode:
+            return
+        n = len(self._fp_ops)
+        self._fp_i64 = torch.zeros(max(n, 1) * self.B, 4, dtype=torch.int64, device=self.device)      # (the kernel sees uint64)
+        self.fingerprint_rec = self._fp_i64.view(torch.uint64)[:n * self.B].view(n, self.B, 4)
+        for i, p in enumerate(self._fp_ops):
+            p.rec = self._fp_i64.data_ptr() + 32 * self.B * i
+            p._keep = tuple(p._keep) + (self._fp_i64,)
+        clear = self._fp_clear[1]
+        clear.rec, clear.n_records, clear._keep = self._fp_i64.data_ptr(), n * self.B, (self._fp_i64,)
+        self.fingerprint_names = torch.tensor(list(b"".join(l.encode() + b"\0" for l in self.fingerprint_labels)) or [0], dtype=torch.uint8, device=self.device)
+
+    def fingerprint(self):
+        """Synchronise and return [(label, uint64 [B, 4])] of the most recent run or replay, in program order: {s0, s1, elements, 0} per image
+        (the contract of i2i_digest_params).  Compare two of them with digest.first_diff."""
+        assert self.fingerprint_mode, "this plan has no fingerprints (ForwardPlan(fingerprint=...))"
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(self.device)
+        rec = self._fp_i64.cpu().view(torch.uint64)[:len(self.fingerprint_labels) * self.B].view(len(self.fingerprint_labels), self.B, 4)
+        return [(label, rec[i].clone()) for i, label in enumerate(self.fingerprint_labels)]
 
     def health_reset(self):
         """Zero every record, and on a per-image plan the verdict rows (fills on the current stream; asynchronous)."""

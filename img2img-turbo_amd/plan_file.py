@@ -28,6 +28,13 @@ Plans with per-image health (--health-per-image with --health; ForwardPlan(healt
 most recent run), "health_names" unchanged, and "verdict" (16 * B bytes: one row of four uint32 {first_bad, first_over, runs, bad_runs} per
 image, written by the program's last op, i2i_scan_verdict_params; totals over the runs).  Export zeroes both; examples/batch_health_host.c
 prints one line per request.
+Plans built with fingerprint= (--fingerprint io|stages|all; ForwardPlan(fingerprint=...)) have "fingerprint" (n_taps x B x 4 uint64, tap-major,
+one i2i_digest_params record {s0, s1, elements, 0} per tap and image; the program zeroes them at the start of every run) and
+"fingerprint_names" (the tap labels, NUL-terminated like "health_names"): examples/fingerprint_host.c.
+Self-verifying files (--digests; export_plan(digests=True)): behind the data the file stores one i2i_digest_params record -- the buffer as
+bytes, index0 = 0, computed on the exporting device -- for every buffer that is saved with contents, that no op of the forward writes and
+that no io name exposes: the weights, constants and tables.  i2i_plan_verify() digests them again where they were loaded and names the first
+buffer that differs.  The section is optional and trailing: a file exported without the flag is byte for byte what it always was.
 
 This replaces the reference's ``model(...)`` call (src/pix2pix_turbo.py:186-219, src/cyclegan_turbo.py:241-254) for hosts that are not
 Python; the planner itself (route queries, tile choices, buffer recycling) stays in plan.py and runs once, at export.
@@ -42,6 +49,16 @@ from . import _capi as K
 
 MAGIC = b"I2IPLAN1"
 MAGIC_LIVE = b"I2IPLAN2"      # exported with live_scale: the header also counts the scale program's ops, stored after the forward's
+MAGIC_DIGESTS = b"I2IDIGS1"   # the optional trailing section of a self-verifying file (csrc/plan_file.hip has the layout)
+
+# pointer fields an op WRITES through (everything else it only reads): a buffer the forward writes is state of a run, not a constant, and
+# gets no digest
+_WRITES = {K.OP_IGEMM: ("c", "c2", "ws", "gn_part"), K.OP_GN_STATS: ("partial", "ss", "counters"), K.OP_GN_APPLY: ("y",), K.OP_LAYERNORM: ("y",),
+           K.OP_SOFTMAX: ("p",), K.OP_ATTENTION: ("o", "ws"), K.OP_NCHW_TO_NHWC: ("y",), K.OP_NHWC_TO_NCHW: ("y",), K.OP_POSTERIOR: ("u", "u_f32"),
+           K.OP_DDPM_POSTQUANT: ("y",), K.OP_EMBED: ("y",), K.OP_LORA_MERGE: ("dst", "colsum", "bias_out"), K.OP_RESIZE_U8: ("dst",), K.OP_NOP: (),
+           K.OP_CANNY_U8: ("dst", "ws"), K.OP_RANDN: ("dst", "state"), K.OP_TWIN_FOLD: ("dst", "bias"), K.OP_SCAN: ("rec",),
+           K.OP_RANDN_BATCH: ("dst", "states"), K.OP_CANNY_U8_BATCH: ("dst", "ws"), K.OP_RESIZE_U8_RAGGED: ("dst", "bad_mask"),
+           K.OP_SCAN_BATCH: ("rec",), K.OP_SCAN_VERDICT: ("rec", "verdict"), K.OP_CANNY_AUTO_THR: ("thr", "median2", "ws"), K.OP_DIGEST: ("rec",)}
 
 
 def _pointer_fields():
@@ -74,7 +91,7 @@ def scale_program_of(plan):
     return prog.freeze()
 
 
-def export_plan(plan, path, extra_tensors=(), live_scale=False):
+def export_plan(plan, path, extra_tensors=(), live_scale=False, digests=False):
     """Write ``plan`` (a ForwardPlan) to ``path``.  Returns a small summary dict.  The plan must not be replaying while this runs
     (the buffers' contents are read back through torch).
 
@@ -85,7 +102,10 @@ def export_plan(plan, path, extra_tensors=(), live_scale=False):
     The packed weights are SHARED by every plan of a model and hold whatever LoRA / skip scale ``r`` was merged last (another plan's
     ``r``, or 1.0 after a deterministic plan ran): ``plan._prepare()`` re-merges them at THIS plan's ``r`` before anything is read
     back, and refuses a plan whose buffers were released (plan-cache eviction).  A plan with health scans is exported with zeroed records:
-    ``plan.health_reset()`` runs first, so read ``health_report()`` before exporting if the counts matter."""
+    ``plan.health_reset()`` runs first, so read ``health_report()`` before exporting if the counts matter.
+
+    ``digests=True``: the file ends with the digest section (see the module text) and i2i_plan_verify() works on it; on a live_scale file the
+    records describe the weights as merged at the export scale."""
     plan._prepare()
     named = {"x": plan.x_in, "ctx": plan.ctx, "eps": plan.eps, "out": plan.out}
     if getattr(plan, "noise", None) is not None:
@@ -104,11 +124,13 @@ def export_plan(plan, path, extra_tensors=(), live_scale=False):
         named["health"], named["health_names"] = plan._health_i64, plan.health_names
         if getattr(plan, "health_per_image", False):       # (health_reset zeroed the rows too)
             named["verdict"] = plan._verdict_i32
+    if getattr(plan, "fingerprint_mode", None):   # the records (scratch: the program zeroes them itself) and their labels
+        named["fingerprint"], named["fingerprint_names"] = plan._fp_i64, plan.fingerprint_names
     gn_scratch = [t for t in (getattr(plan, n, None) for n in ("gn_partial", "gn_ss", "gn_counters")) if t is not None]
     if getattr(plan, "canny", False):
         gn_scratch += [plan.canny_edges, plan.canny_ws] + ([plan.canny_auto_ws] if getattr(plan, "canny_auto", False) else [])
-    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "canny_sigma", "seed", "health", "health_names", "verdict"), holders=[plan] + list(extra_tensors), device=plan.device,
-                          scale_prog=scale_program_of(plan) if live_scale else None)
+    return export_program(plan.prog, path, named, scratch=list(plan.pool.all) + gn_scratch, keep_contents=("canny_thr", "canny_sigma", "seed", "health", "health_names", "verdict", "fingerprint_names"), holders=[plan] + list(extra_tensors), device=plan.device,
+                          scale_prog=scale_program_of(plan) if live_scale else None, digests=digests, lib=plan.lib)
 
 
 def export_text_plan(encoder, batch, path):
@@ -122,11 +144,23 @@ def export_text_plan(encoder, batch, path):
     return export_program(tp.prog, path, {"ids": tp.ids, "ctx": tp.out}, scratch=list(tp._keep), holders=[tp, encoder.w], device=encoder.device)
 
 
-def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep_contents=(), scale_prog=None):
+def _digest_storage(t, lib):
+    """The i2i_digest record of t's whole storage as bytes (index0 = 0), computed on its device, in pieces of 2^30 bytes."""
+    from .digest import digest
+    s = t.untyped_storage()
+    flat = torch.empty(0, dtype=torch.uint8, device=t.device).set_(s, 0, (s.nbytes(),), (1,))
+    tot = torch.zeros(4, dtype=torch.int64)
+    for at in range(0, s.nbytes(), 1 << 30):
+        tot += digest(flat[at:at + (1 << 30)], index0=at, lib=lib)[0].view(torch.int64)      # (int64 adds wrap like uint64 ones)
+    return [int(v) & (2 ** 64 - 1) for v in tot.tolist()]
+
+
+def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep_contents=(), scale_prog=None, digests=False, lib=None):
     """The file writer behind both: ``prog`` (a frozen _capi.Program), ``named`` boundary tensors, ``scratch`` tensors whose contents need
     not be saved (zero-filled at load, like the boundary buffers), ``holders``: objects / tensors that own anything else the ops point at,
     ``keep_contents``: names of boundary tensors that are saved WITH their contents (parameters with a meaningful default).
-    ``scale_prog``: a second frozen program stored after ``prog`` (the live_scale form, see export_plan)."""
+    ``scale_prog``: a second frozen program stored after ``prog`` (the live_scale form, see export_plan).  ``digests``: append the digest
+    section, computed with ``lib`` (default: the product library)."""
     assert prog.array is not None, "the program is not frozen"
     progs = [prog] + ([scale_prog] if scale_prog is not None else [])
     all_ops = [(pg, i) for pg in progs for i in range(pg.n)]      # the concatenated op array relocations index
@@ -164,7 +198,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
 
     # ---- relocations
     fields = _pointer_fields()
-    relocs, used = [], set()
+    relocs, used, volatile = [], set(), set()    # volatile: buffers the forward writes or an io name exposes (no digest)
     for oi, (pg, li) in enumerate(all_ops):
         op = pg.array[li]
         base = C.addressof(op)
@@ -175,11 +209,14 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
             b, o = locate(v, "op %d (%s) field %s" % (oi, pg.labels[li], fname))
             relocs.append((oi, off, b, o))
             used.add(b)
+            if pg is prog and fname in _WRITES[op.opcode]:
+                volatile.add(b)
     io = []
     for name, t in named.items():
         b, o = locate(t.data_ptr(), "boundary buffer " + name)
         io.append((name, b, o, t.numel() * t.element_size()))
         used.add(b)
+        volatile.add(b)
     # ---- compact the buffer table to the storages that are referenced
     remap, bufs = {}, []
     for b in sorted(used):
@@ -212,13 +249,25 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
             host = flat.cpu().numpy()
             f.write(host.tobytes())
             data_bytes += nbytes
-    return {"ops": prog.n, "scale_ops": scale_prog.n if scale_prog is not None else 0, "buffers": len(bufs), "relocations": len(relocs), "data_bytes": data_bytes,
+        digest_recs = []
+        if digests:
+            for b in sorted(used):
+                nbytes, kind, t = bufs[remap[b]]
+                if kind == 1 and b not in volatile:
+                    s0, s1, n, _ = _digest_storage(t, lib)
+                    assert n == nbytes, (n, nbytes)
+                    digest_recs.append((remap[b], s0, s1, n))
+            f.write(MAGIC_DIGESTS + struct.pack("<2I", len(digest_recs), 0))
+            for b, s0, s1, n in digest_recs:
+                f.write(struct.pack("<IIQQQ", b, 0, s0, s1, n))
+    return {"digests": len(digest_recs), "digest_bytes": sum(r[3] for r in digest_recs),
+            "ops": prog.n, "scale_ops": scale_prog.n if scale_prog is not None else 0, "buffers": len(bufs), "relocations": len(relocs), "data_bytes": data_bytes,
             "scratch_bytes": sum(b[0] for b in bufs if b[1] == 0), "io": {n: sz for n, _, _, sz in io}}
 
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH | --canny-auto SIGMA]] [--seed N | --seeds S0,S1,..] [--health stages|all [--health-per-image]] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH | --canny-auto SIGMA]] [--seed N | --seeds S0,S1,..] [--health stages|all [--health-per-image]] [--fingerprint io|stages|all] [--digests] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -252,6 +301,11 @@ def main(argv=None):
     ap.add_argument("--health-per-image", action="store_true", help="with --health: one record per scanned tensor AND image ('health' holds "
                     "taps x batch x 8 uint64, zeroed by the program at the start of every run) and the buffer 'verdict' (16 bytes per image: "
                     "uint32 {first_bad, first_over, runs, bad_runs}; first_bad = 1 + the index of the first tap at which that image held a NaN / Inf)")
+    ap.add_argument("--fingerprint", default=None, choices=["io", "stages", "all"], help="device fingerprints in the program (ForwardPlan(fingerprint=...)): "
+                    "the file gets the buffers 'fingerprint' (4 uint64 {s0, s1, elements, 0} per tap and image, tap-major, zeroed by the program at the "
+                    "start of every run) and 'fingerprint_names' (the tap labels)")
+    ap.add_argument("--digests", action="store_true", help="self-verifying file: store one digest per weight / constant buffer behind the data; "
+                    "i2i_plan_verify() recomputes them on the device that loaded the file")
     ap.add_argument("--live-scale", action="store_true", help="also store the scale program (per-layer merges, TwinConv fold, their fp32 masters and "
                     "LoRA factors): a host then moves the LoRA scale / skip gamma with i2i_plan_set_scale() instead of exporting one file per scale")
     ap.add_argument("--device", default="cuda:0")
@@ -287,7 +341,7 @@ def main(argv=None):
     H, W = a.size[0], a.size[-1]
     if a.health_per_image and not a.health:
         ap.error("--health-per-image needs --health stages|all")
-    kw = dict(device=a.device, dtype=dt, live_scale=a.live_scale, health=a.health, health_per_image=a.health_per_image)
+    kw = dict(device=a.device, dtype=dt, live_scale=a.live_scale, health=a.health, health_per_image=a.health_per_image, fingerprint=a.fingerprint)
     if a.lib:
         kw["lib"] = K.Library(a.lib)
     if a.synthetic:
@@ -320,7 +374,7 @@ def main(argv=None):
         plan.set_seeds(seeds, 0)
     elif a.seed is not None:
         plan.set_seed(a.seed, 0)
-    info = export_plan(plan, a.out, live_scale=a.live_scale)                 # (re-merges the weights at this plan's r first: plan._prepare)
+    info = export_plan(plan, a.out, live_scale=a.live_scale, digests=a.digests)                 # (re-merges the weights at this plan's r first: plan._prepare)
     print("wrote %s: %d ops%s, %d buffers, %.2f GB of weights, %.2f GB of scratch at load; boundary buffers %s"
           % (a.out, info["ops"], " + %d scale ops" % info["scale_ops"] if a.live_scale else "", info["buffers"], info["data_bytes"] / 1e9, info["scratch_bytes"] / 1e9, info["io"]))
 

@@ -35,7 +35,8 @@ typedef enum {
     I2I_ERR_BAD_ARG = -1,      /* unsupported shape / alignment / null pointer */
     I2I_ERR_LAUNCH = -2,       /* HIP reported an error at launch */
     I2I_ERR_UNSUPPORTED = -3,
-    I2I_ERR_RUNTIME = -4       /* other HIP runtime failure (graph capture, events) */
+    I2I_ERR_RUNTIME = -4,      /* other HIP runtime failure (graph capture, events) */
+    I2I_ERR_MISMATCH = -5      /* i2i_plan_verify: a buffer's digest differs from the one stored in the plan file */
 } i2i_status;
 
 typedef enum {
@@ -62,7 +63,8 @@ typedef enum {
     I2I_OP_RESIZE_U8_RAGGED = 21,  /* ABI 14 addition (see the note above i2i_resize_u8_ragged_params) */
     I2I_OP_SCAN_BATCH = 22,        /* ABI 14 additions (see the note above i2i_scan_batch_params) */
     I2I_OP_SCAN_VERDICT = 23,
-    I2I_OP_CANNY_AUTO_THR = 24     /* ABI 14 addition (see the note above i2i_canny_auto_thr_params) */
+    I2I_OP_CANNY_AUTO_THR = 24,    /* ABI 14 addition (see the note above i2i_canny_auto_thr_params) */
+    I2I_OP_DIGEST = 25             /* ABI 14 addition (see the note above i2i_digest_params) */
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -575,6 +577,61 @@ typedef struct {
     void* ws;                   /* >= i2i_canny_auto_ws_bytes(n), 16-byte aligned; contents irrelevant before and after */
 } i2i_canny_auto_thr_params;
 
+/* ---- ABI 14 addition: device fingerprints (I2I_OP_DIGEST).  Purely additive like the ones above -- one new opcode, one new struct, two new
+ * exported functions (i2i_digest, i2i_plan_verify); no existing struct, opcode number or signature changed and sizeof(i2i_op) did not grow -- so
+ * I2I_ABI_VERSION stays 14.  A library built before the addition is recognised by the missing symbol (i2i_digest), and its plan loader refuses
+ * the new opcode as unknown.
+ *
+ * A position-sensitive, order-independent digest of a tensor view, computed on the device: "did two runs, two GPUs, two hosts compute the
+ * same BITS, and from which stage and which request on did they stop doing so" -- what the health scan cannot say (a finite wrong value: a
+ * corrupted weight, a stale pooled buffer, a flipped byte of a plan file).  A pure read of x; nothing but the records is written.
+ *   VIEW      as i2i_scan_batch_params: `images` views of rows x cols elements (I2I_U8 / I2I_F16 / I2I_BF16 / I2I_F32 = 1 / 2 / 2 / 4 bytes),
+ *             row r of image b at x + b * img_stride + r * ld elements (ld >= cols, img_stride >= (rows - 1) * ld + cols).  Elements
+ *             [cols, ld) of a row and the gaps between images are NEVER read.  x needs the alignment of its element type only.
+ *   INDEX     element p = row * cols + col of an image (pitch pads do not count) has the logical index j = index0 + p (uint64, wraps mod
+ *             2^64); index0 is the same for every image.
+ *   RECORD b  four uint64 {s0, s1, elements, reserved} at rec + b * 32 bytes (rec 8-byte aligned).  The op ADDS into it; the owner zeroes
+ *             it (or I2I_DIGEST_CLEAR does).  reserved is never written (stays 0).
+ *   VALUE     v = the element's bit pattern, zero-extended to 32 bits.  Per element, mod 2^64:
+ *               s0 += H0(j, v)     s1 += H1(j, v)     elements += 1
+ *   MIXERS    integer only, all arithmetic mod 2^64, >> is a logical shift:
+ *               m  = (j * 0x9E3779B97F4A7C15) ^ v
+ *               m ^= m >> 33;  m *= 0xFF51AFD7ED558CCD;  m ^= m >> 33;  m *= 0xC4CEB9FE1A85EC53;  m ^= m >> 33;       H0 = m
+ *               t  = (H0 ^ (H0 >> 31)) * 0xD6E8FEB86659FD93;  H1 = t ^ (t >> 32)
+ *             (H0 is the 64-bit finaliser of MurmurHash3 over the Weyl-stepped index xor the value; H1 is one more multiply / xor-shift
+ *             round on H0 -- a bijection of it -- so the pair (sum of H0, sum of H1) is a 128-bit multiset digest of the per-element 64-bit
+ *             hashes.)  For a fixed j, v -> H0 and v -> H1 are injective: a change of ONE element always changes the record.  Every bit of
+ *             (j, v) flips every bit of (H0, H1) with probability ~1/2 (tests/test_digest_emu.py::test_mixer_avalanche).
+ *   FOLLOWS   Every update is an integer add, so the record is INDEPENDENT of the grid, the order the workgroups arrive in, the alignment
+ *             of x and the pitch, and is BIT-EQUAL between the CPU emulator and the GPU (tests/digest_ref.py is the oracle of this text).
+ *             digest(A || B) = digest(A) + digest(B, index0 = len A), field by field: a buffer can be digested in pieces.
+ *             The value is the bit pattern: -0.0 != +0.0, and every NaN payload counts.
+ *   SCOPE     This detects ACCIDENTS (bit rot, truncation, stale or mixed-up buffers, nondeterminism).  It is NOT cryptographic: the
+ *             mixers are public and invertible, anyone can construct a second tensor with the same record.
+ *   KIND      I2I_DIGEST_ADD    the above.  images == 0 or rows * cols == 0 is a successful no-op (nothing written, x / rec not needed).
+ *             I2I_DIGEST_CLEAR  zeroes the n_records records (all four words each) from rec on, nothing else -- as I2I_VERDICT_CLEAR does
+ *                               for the health records -- so a planned program needs no host fill.  Only rec / n_records are read.
+ * ADD is one launch: the grid is (slices of an image) x (images), capped in total, grid-stride loops; 16-byte loads on the 16-byte aligned
+ * part of every image (several in flight per lane), element loads on its head and tail; every lane keeps s0 / s1 in 64-bit registers,
+ * reduced lanes -> wave -> workgroup (LDS) -> ONE agent-scope add per sum, workgroup and image; `elements` comes from one lane per image.
+ * No allocation, no synchronisation, no read-back; graph-capturable.
+ * Errors (I2I_ERR_BAD_ARG, nothing written): null params; an unknown kind; rec null or not 8-byte aligned; (CLEAR) n_records < 0 or past
+ * 2^40; (ADD) images < 0, negative rows / cols, ld < cols, img_stride smaller than one image's extent (or sizes whose products leave 2^61),
+ * x null or not aligned to its element, a dtype outside the four above. */
+typedef enum { I2I_DIGEST_ADD = 0, I2I_DIGEST_CLEAR = 1 } i2i_digest_kind;
+typedef struct {
+    const void* x;
+    int32_t images;                    /* >= 0 */
+    int32_t cols;
+    int64_t rows, ld;                  /* rows per image; row pitch in elements, >= cols */
+    int64_t img_stride;                /* elements between image starts */
+    uint64_t index0;                   /* logical index of the first element of EVERY image */
+    uint64_t* rec;                     /* record of image 0; record b at rec + 4 * b words */
+    int32_t kind;                      /* i2i_digest_kind */
+    int32_t reserved;
+    int64_t n_records;                 /* I2I_DIGEST_CLEAR: records to zero */
+} i2i_digest_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -605,6 +662,7 @@ typedef struct {
         i2i_scan_batch_params scan_batch;
         i2i_scan_verdict_params scan_verdict;
         i2i_canny_auto_thr_params canny_auto_thr;
+        i2i_digest_params digest;
     } u;
 } i2i_op;
 
@@ -648,6 +706,7 @@ int i2i_scan_batch(const i2i_scan_batch_params* p, int dtype, void* stream);    
 int i2i_scan_verdict(const i2i_scan_verdict_params* p, int dtype, void* stream);       /* dtype ignored; one launch */
 int i2i_canny_auto_thr(const i2i_canny_auto_thr_params* p, int dtype, void* stream);   /* dtype ignored (uint8 data); three launches */
 size_t i2i_canny_auto_ws_bytes(int n);                                                 /* bytes of i2i_canny_auto_thr_params.ws (0 for n < 1) */
+int i2i_digest(const i2i_digest_params* p, int dtype, void* stream);                   /* one launch; dtype = element type of x (I2I_U8 allowed) */
 /* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
  * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
  * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
@@ -728,6 +787,20 @@ int i2i_plan_destroy(void* plan);
  * returns I2I_ERR_UNSUPPORTED.  i2i_plan_ops() is the forward alone either way. */
 int i2i_plan_has_scale(void* plan);
 int i2i_plan_set_scale(void* plan, float r, float gamma, void* stream);
+/* Self-verifying plan files (ABI 14 addition).  A file exported with digests (plan_file.py --digests / export_plan(digests=True)) ends with
+ * an optional section behind the data: "I2IDIGS1", u32 count, u32 pad, then count x { u32 buf; u32 pad; u64 s0, s1, elements } -- one
+ * i2i_digest_params record (I2I_U8 view of the whole buffer, index0 = 0, computed on the exporting device) for every buffer that is saved
+ * with contents AND that no op of the program writes and no io name exposes: the weights, constants and tables.  A file without the
+ * section is byte for byte what it was before and loads as before.  The loader checks the section like the rest of the file (count against
+ * the buffer table and the bytes left in the file, every buf index in range, kind 1, no duplicates, elements == the buffer's size); a
+ * malformed section fails the load.  Plans built with fingerprint= also have the io names "fingerprint" (taps x B x 4 uint64, tap-major:
+ * one i2i_digest_params record per tap and image, zeroed by the program itself at the start of every run) and "fingerprint_names" (the tap
+ * labels, NUL-terminated, as "health_names"): examples/fingerprint_host.c.
+ * i2i_plan_verify digests those buffers again on the device (on `stream`, which it synchronises, as i2i_plan_read does) and compares:
+ * 0 = all equal; I2I_ERR_MISMATCH = the first differing buffer's index in *first_bad_buffer (if given) and in i2i_last_error() with both
+ * records; I2I_ERR_UNSUPPORTED = the file carries no digests.  On a live-scale file the records describe the weights AS EXPORTED: after
+ * i2i_plan_set_scale to another r the merged weights differ by design, and back at the export scale they verify again. */
+int i2i_plan_verify(void* plan, void* stream, int* first_bad_buffer);
 
 #ifdef __cplusplus
 }
