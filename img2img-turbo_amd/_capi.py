@@ -27,6 +27,8 @@ OP_RESIZE_U8_RAGGED = 21
 OP_SCAN_BATCH, OP_SCAN_VERDICT = 22, 23      # per-image health (i2i_scan_batch_params / i2i_scan_verdict_params)
 OP_CANNY_AUTO_THR = 24                      # automatic per-image Canny thresholds (i2i_canny_auto_thr_params)
 OP_DIGEST = 25                              # device fingerprints (i2i_digest_params)
+OP_REPEAT = 26                              # variations: image-major replication of up to 8 tensors (i2i_repeat_params)
+REPEAT_MAX_SEGMENTS = 8
 DIGEST_ADD, DIGEST_CLEAR = 0, 1             # i2i_digest_kind
 ERR_UNSUPPORTED, ERR_MISMATCH = -3, -5      # i2i_status values callers tell apart (i2i_plan_verify)
 FILTER_LANCZOS, FILTER_BICUBIC = 0, 1       # i2i_resample_filter
@@ -172,6 +174,13 @@ class DigestParams(C.Structure):
                 ("kind", i32), ("reserved", i32), ("n_records", i64)]
 
 
+class RepeatParams(C.Structure):
+    """i2i_repeat_params with its by-value table seg[8] = {src, dst, bytes_per_image} written out flat (src0, dst0, bytes0, src1, ..): the same
+    memory, and every pointer is a plain member, which is what the plan exporter's relocation scan walks."""
+    _fields_ = ([("batch", i32), ("variations", i32), ("n_segments", i32), ("reserved", i32)]
+                + [f for s in range(REPEAT_MAX_SEGMENTS) for f in (("src%d" % s, vp), ("dst%d" % s, vp), ("bytes%d" % s, i64))])
+
+
 class NopParams(C.Structure):
     _fields_ = [("unused", i32)]
 
@@ -184,7 +193,7 @@ class _OpUnion(C.Union):
                 ("nop", NopParams), ("canny_u8", CannyU8Params), ("randn", RandnParams), ("twin_fold", TwinFoldParams), ("scan", ScanParams),
                 ("randn_batch", RandnBatchParams), ("canny_u8_batch", CannyU8BatchParams), ("resize_u8_ragged", ResizeU8RaggedParams),
                 ("scan_batch", ScanBatchParams), ("scan_verdict", ScanVerdictParams), ("canny_auto_thr", CannyAutoThrParams),
-                ("digest", DigestParams)]
+                ("digest", DigestParams), ("repeat", RepeatParams)]
 
 
 class Op(C.Structure):
@@ -197,7 +206,7 @@ _FIELD_OF = {OP_IGEMM: "igemm", OP_GN_STATS: "gn_stats", OP_GN_APPLY: "gn_apply"
              OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8", OP_RANDN: "randn", OP_TWIN_FOLD: "twin_fold", OP_SCAN: "scan",
              OP_RANDN_BATCH: "randn_batch", OP_CANNY_U8_BATCH: "canny_u8_batch", OP_RESIZE_U8_RAGGED: "resize_u8_ragged",
              OP_SCAN_BATCH: "scan_batch", OP_SCAN_VERDICT: "scan_verdict", OP_CANNY_AUTO_THR: "canny_auto_thr",
-             OP_DIGEST: "digest"}
+             OP_DIGEST: "digest", OP_REPEAT: "repeat"}
 
 EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", "i2i_igemm", "i2i_igemm_gn_parts", "i2i_igemm_route", "i2i_gn_stats",
            "i2i_gn_apply", "i2i_nop", "i2i_calib_mfma", "i2i_calib_stream", "i2i_layernorm", "i2i_softmax", "i2i_attention", "i2i_nchw_to_nhwc",
@@ -207,7 +216,7 @@ EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", 
            "i2i_merge_group_create", "i2i_merge_group_run", "i2i_merge_group_destroy", "i2i_run", "i2i_run_timed",
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
-           "i2i_plan_has_scale", "i2i_plan_set_scale", "i2i_digest", "i2i_plan_verify"]
+           "i2i_plan_has_scale", "i2i_plan_set_scale", "i2i_digest", "i2i_plan_verify", "i2i_repeat"]
 
 
 class I2IError(RuntimeError):
@@ -260,7 +269,7 @@ class Library:
         L.i2i_sizeof_op.restype = C.c_size_t
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
                      "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
-                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr", "i2i_digest"):
+                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr", "i2i_digest", "i2i_repeat"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]

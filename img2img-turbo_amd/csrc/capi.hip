@@ -54,6 +54,7 @@ int dispatch(const i2i_op& op, void* stream) {
         case I2I_OP_SCAN_VERDICT: return i2i_scan_verdict(&op.u.scan_verdict, op.dtype, stream);
         case I2I_OP_CANNY_AUTO_THR: return i2i_canny_auto_thr(&op.u.canny_auto_thr, op.dtype, stream);
         case I2I_OP_DIGEST: return i2i_digest(&op.u.digest, op.dtype, stream);
+        case I2I_OP_REPEAT: return i2i_repeat(&op.u.repeat, op.dtype, stream);
         default: return i2i::fail(I2I_ERR_BAD_ARG, "run: unknown opcode %d", op.opcode);
     }
 }

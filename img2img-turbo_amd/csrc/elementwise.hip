@@ -3,7 +3,10 @@
 //   DiagonalGaussianDistribution.sample()*scaling_factor + the stochastic mix (src/pix2pix_turbo.py:198,210),
 //   DDPMScheduler.step + /scaling_factor + post_quant_conv (src/pix2pix_turbo.py:200-203),
 //   the seeded Gaussian noise of the callers (torch.manual_seed + torch.randn, src/inference_paired.py:58-60): Philox4x32-10 + Box-Muller,
-//   the numerical health scan of an activation tensor (NaN / Inf / near-saturation counts into a device record; no reference counterpart).
+//   the numerical health scan of an activation tensor (NaN / Inf / near-saturation counts into a device record; no reference counterpart),
+//   the image-major replication of the encoder's outputs for ForwardPlan(variations = V) (i2i_repeat: one read, V stores per vector).
+#include <string.h>
+
 #include <type_traits>
 
 #include "i2i_dev.h"
@@ -704,7 +707,94 @@ inline unsigned grid_for(int64_t n) {
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
+// ---- repeat_interleave of up to 8 batch-outermost tensors in one launch (the contract is the comment of i2i_repeat_params).  A 1-D grid
+// over the 16-byte vectors of all segments together: segment s owns the workgroups prefix[s] .. prefix[s + 1) and a workgroup copies
+// REPEAT_CHUNK consecutive source vectors of it.  The segment of a workgroup is found from blockIdx alone (wave-uniform; the loop below is
+// unrolled, so the by-value table is read at constant offsets of the kernel-argument segment).  Every source vector is loaded once -- the
+// loads of a lane are issued together -- and stored V times.  All byte offsets are 64-bit; only the split of a vector's index into (image,
+// vector in the image) runs in 32 bits: from the workgroup's first vector (one 64-bit division, uniform) a lane is less than
+// vecs + REPEAT_CHUNK <= 2^31 + 1024 vectors away.
+constexpr int REPEAT_THREADS = 256;
+constexpr int REPEAT_UNROLL = 4;
+constexpr int REPEAT_CHUNK = REPEAT_THREADS * REPEAT_UNROLL;       // source vectors per workgroup (16 KiB)
+
+struct RepeatArgs {
+    const u32x4* src[I2I_REPEAT_MAX_SEGMENTS];
+    u32x4* dst[I2I_REPEAT_MAX_SEGMENTS];
+    int64_t vecs[I2I_REPEAT_MAX_SEGMENTS];          // 16-byte vectors per image (>= 1 for every segment that owns a workgroup)
+    int64_t total[I2I_REPEAT_MAX_SEGMENTS];         // batch * vecs
+    uint32_t prefix[I2I_REPEAT_MAX_SEGMENTS + 1];   // first workgroup of segment s; an empty segment has prefix[s + 1] == prefix[s]
+    int32_t n_seg, variations;
+};
+
+__global__ __launch_bounds__(REPEAT_THREADS) void repeat_kernel(const RepeatArgs a) {
+    const uint32_t bid = blockIdx.x;
+    const u32x4* src = a.src[0];
+    u32x4* dst = a.dst[0];
+    int64_t vecs = a.vecs[0], total = a.total[0];
+    uint32_t first = a.prefix[0];
+#pragma unroll
+    for (int s = 1; s < I2I_REPEAT_MAX_SEGMENTS; ++s) {
+        if (s < a.n_seg && a.prefix[s] <= bid) src = a.src[s], dst = a.dst[s], vecs = a.vecs[s], total = a.total[s], first = a.prefix[s];
+    }
+    const int64_t base = (int64_t)(bid - first) * REPEAT_CHUNK;     // first source vector of this workgroup (< total by construction)
+    const int64_t b0 = base / vecs;
+    const uint32_t r0 = (uint32_t)(base - b0 * vecs), vecs32 = (uint32_t)vecs;
+    const int64_t V = a.variations;
+    u32x4 v[REPEAT_UNROLL];
+    int64_t out[REPEAT_UNROLL];
+#pragma unroll
+    for (int u = 0; u < REPEAT_UNROLL; ++u) {
+        const uint32_t t = (uint32_t)(u * REPEAT_THREADS) + threadIdx.x;
+        const int64_t i = base + t;
+        out[u] = -1;
+        if (i < total) {
+            const uint32_t off = r0 + t, q = off / vecs32;          // (r0 < vecs <= 2^31, t < 1024: no wrap)
+            out[u] = (b0 + q) * V * vecs + (off - q * vecs32);      // image-major: slot b * V + 0
+            v[u] = src[i];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < REPEAT_UNROLL; ++u) {
+        if (out[u] < 0) continue;
+        u32x4* d = dst + out[u];
+        for (int64_t k = 0; k < V; ++k, d += vecs) *d = v[u];
+    }
+}
+
 }  // namespace
+
+extern "C" int i2i_repeat(const i2i_repeat_params* p, int /*dtype*/, void* stream) {
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "repeat: null params");
+    if (p->variations < 1) return i2i::fail(I2I_ERR_BAD_ARG, "repeat: variations = %d < 1", p->variations);
+    if (p->batch < 0) return i2i::fail(I2I_ERR_BAD_ARG, "repeat: batch = %d < 0", p->batch);
+    if (p->n_segments < 0 || p->n_segments > I2I_REPEAT_MAX_SEGMENTS)
+        return i2i::fail(I2I_ERR_BAD_ARG, "repeat: n_segments = %d is outside 0 .. %d", p->n_segments, I2I_REPEAT_MAX_SEGMENTS);
+    RepeatArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_seg = p->n_segments, a.variations = p->variations;
+    uint64_t blocks = 0;
+    for (int s = 0; s < p->n_segments; ++s) {
+        const i2i_repeat_segment& g = p->seg[s];
+        if (g.bytes_per_image < 0 || (g.bytes_per_image & 15) || g.bytes_per_image >= ((int64_t)1 << 35))
+            return i2i::fail(I2I_ERR_BAD_ARG, "repeat: segment %d: bytes_per_image = %lld is not a multiple of 16 in 0 .. 2^35 - 16", s, (long long)g.bytes_per_image);
+        if (!g.src || ((uintptr_t)g.src & 15)) return i2i::fail(I2I_ERR_BAD_ARG, "repeat: segment %d: src is null or not 16-byte aligned", s);
+        if (!g.dst || ((uintptr_t)g.dst & 15)) return i2i::fail(I2I_ERR_BAD_ARG, "repeat: segment %d: dst is null or not 16-byte aligned", s);
+        const int64_t big = (int64_t)1 << 61;
+        if (p->batch > 0 && g.bytes_per_image > big / p->batch / p->variations)
+            return i2i::fail(I2I_ERR_BAD_ARG, "repeat: segment %d: batch * variations * bytes_per_image = %d * %d * %lld is too large", s, p->batch, p->variations,
+                             (long long)g.bytes_per_image);
+        a.src[s] = (const u32x4*)g.src, a.dst[s] = (u32x4*)g.dst;
+        a.vecs[s] = g.bytes_per_image / 16, a.total[s] = a.vecs[s] * p->batch;
+        a.prefix[s] = (uint32_t)blocks;
+        blocks += (uint64_t)((a.total[s] + REPEAT_CHUNK - 1) / REPEAT_CHUNK);
+        if (blocks > 0x7FFFFFFFull) return i2i::fail(I2I_ERR_BAD_ARG, "repeat: segments 0 .. %d need more than 2^31 - 1 workgroups (bytes_per_image too large)", s);
+    }
+    for (int s = p->n_segments; s <= I2I_REPEAT_MAX_SEGMENTS; ++s) a.prefix[s] = (uint32_t)blocks;
+    if (blocks == 0) return I2I_OK;
+    hipLaunchKernelGGL(repeat_kernel, dim3((unsigned)blocks), dim3(REPEAT_THREADS), 0, (hipStream_t)stream, a);
+    return i2i::check_launch("repeat");
+}
 
 extern "C" int i2i_digest(const i2i_digest_params* p, int dtype, void* stream) {
     if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "digest: null params");

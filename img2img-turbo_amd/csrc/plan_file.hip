@@ -116,7 +116,16 @@ const std::vector<size_t>& ptr_fields(int opcode) {
     static const std::vector<size_t> canny_auto = {PF(canny_auto_thr, src), PF(canny_auto_thr, sigma_q16), PF(canny_auto_thr, thr),
                                                    PF(canny_auto_thr, median2), PF(canny_auto_thr, ws)};
     static const std::vector<size_t> digest = {PF(digest, x), PF(digest, rec)};
+    static const std::vector<size_t> repeat = [] {      // seg[s].src / seg[s].dst of the by-value table (entries behind n_segments stay null)
+        std::vector<size_t> v;
+        for (size_t s = 0; s < I2I_REPEAT_MAX_SEGMENTS; ++s) {
+            v.push_back(PF(repeat, seg) + s * sizeof(i2i_repeat_segment) + offsetof(i2i_repeat_segment, src));
+            v.push_back(PF(repeat, seg) + s * sizeof(i2i_repeat_segment) + offsetof(i2i_repeat_segment, dst));
+        }
+        return v;
+    }();
     switch (opcode) {
+        case I2I_OP_REPEAT: return repeat;
         case I2I_OP_DIGEST: return digest;
         case I2I_OP_CANNY_AUTO_THR: return canny_auto;
         case I2I_OP_SCAN_BATCH: return scan_batch;

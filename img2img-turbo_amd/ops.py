@@ -270,6 +270,21 @@ def digest_clear(rec, *, n_records):
     return K.OP_DIGEST, _keep(p, rec)
 
 
+def repeat(pairs, *, batch, variations, bytes_per_image=None):
+    """dst_s = src_s.repeat_interleave(variations, 0) for up to 8 (src, dst) tensor pairs in one launch (the contract: i2i_repeat_params):
+    src_s holds ``batch`` contiguous images, dst_s ``batch * variations``, image-major.  ``bytes_per_image``: one value per pair (default:
+    the source's bytes / batch)."""
+    p = K.RepeatParams()
+    pairs = list(pairs)
+    p.batch, p.variations, p.n_segments = int(batch), int(variations), len(pairs)
+    for s, (src, dst) in enumerate(pairs[:K.REPEAT_MAX_SEGMENTS]):      # (more than 8: n_segments says so and the library refuses the op)
+        n = (src.numel() * src.element_size() // max(int(batch), 1)) if bytes_per_image is None else int(bytes_per_image[s])
+        setattr(p, "src%d" % s, ptr(src))
+        setattr(p, "dst%d" % s, ptr(dst))
+        setattr(p, "bytes%d" % s, n)
+    return K.OP_REPEAT, _keep(p, *[t for pair in pairs for t in pair])
+
+
 def nhwc_to_nchw(x, y, *, n, c, h, w, ldx, clamp=0, mul=0.0, add=0.0):
     """y: NCHW float tensor, or a uint8 HWC image batch [n, h, w, c] (then y = trunc(clamp01(x*mul+add)*255))."""
     p = K.NhwcToNchwParams()

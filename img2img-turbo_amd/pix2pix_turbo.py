@@ -228,7 +228,7 @@ class TurboGeneratorBase(torch.nn.Module):
                 for pk in self._packers.values():
                     pk.set_scale(r, r)
 
-    def get_plan(self, B, H, W, stochastic=False, r=1.0, direction="a2b", ctx_batch=1, u8_io=None, canny=False, rng=False) -> ForwardPlan:
+    def get_plan(self, B, H, W, stochastic=False, r=1.0, direction="a2b", ctx_batch=1, u8_io=None, canny=False, rng=False, _variations=1) -> ForwardPlan:
         """The cached plan for this shape.  `r` is not part of the key (device addresses do not depend on it): ONE plan object
         per key, which records the r of the most recent get_plan() for that key and re-applies it whenever it runs
         (ForwardPlan.before_run).  Plans of DIFFERENT keys (a stochastic and a deterministic one, two sizes) can be held and
@@ -248,7 +248,11 @@ class TurboGeneratorBase(torch.nn.Module):
                + ((("canny_per_image",) if canny == "per_image" else (("canny_auto",) if canny == "auto" else (True,))) if canny else ())
                + ((("rng_per_image",) if rng == "per_image" else ("rng",)) if rng else ())
                + (("health", self.health, self.health_limit) if self.health else ()) + (("health_per_image",) if self.health_per_image else ())
-               + (("fingerprint", self.fingerprint_mode) if self.fingerprint_mode else ()))
+               + (("fingerprint", self.fingerprint_mode) if self.fingerprint_mode else ())
+               + (("variations", int(_variations)) if int(_variations) != 1 else ()))      # (1 = the key, and the plan, of a call without it)
+        if int(_variations) > 1 and self.health_per_image:
+            raise ValueError("variations=%d on a model with health_per_image=True: per-image health of a variations plan is not supported "
+                             "(use whole-batch health)" % int(_variations))
         if key in self._plans:
             self._plans.move_to_end(key)
         else:
@@ -265,6 +269,8 @@ class TurboGeneratorBase(torch.nn.Module):
                     opts["health_per_image"] = True
             if self.fingerprint_mode:
                 opts["fingerprint"] = self.fingerprint_mode
+            if int(_variations) != 1:
+                opts["variations"] = int(_variations)
             with self._on_device():
                 self._plans[key] = ForwardPlan(self.lib, self.weights, B, H, W, self.dtype_, self.device_, stochastic=stochastic,
                                                r=self._r, direction=direction, ctx_batch=ctx_batch, fuse_gn=self.fuse_gn,
@@ -300,6 +306,9 @@ class TurboGeneratorBase(torch.nn.Module):
         """Copy one batch into the plan's static boundary buffers (device-to-device when the inputs are already resident).  ``eps=None``:
         the plan draws its own noise (rng plans)."""
         plan.x_in.copy_(x)
+        V = getattr(plan, "V", 1)
+        if V > 1 and plan.ctx_batch > 1 and caption_enc.numel() * V == plan.ctx.numel():      # one caption per INPUT image: image-major rows
+            caption_enc = caption_enc.reshape((plan.B,) + tuple(plan.ctx.shape[1:])).to(plan.ctx.device).repeat_interleave(V, 0)
         plan.ctx.copy_(caption_enc.reshape(plan.ctx.shape))
         if eps is not None:
             plan.eps.copy_(eps)
@@ -328,13 +337,20 @@ class TurboGeneratorBase(torch.nn.Module):
             return plan.out.clone()
 
 
-def seed_argument(seed, B):
-    """``seed=`` of the forwards: None, one int (one noise state for the batch), or a sequence of B ints (one per image) -> None | int | list."""
+def seed_argument(seed, B, V=1):
+    """``seed=`` of the forwards: None, one int (one noise state for the batch), or a sequence of B ints (one per image) -> None | int | list.
+    With ``variations=V`` the sequence is nested [B][V] or flat with B * V entries; the list returned is flat, in output order (b * V + v)."""
     if seed is None or isinstance(seed, numbers.Integral):
         return seed
+    seed = list(seed)
+    if V > 1 and len(seed) == B and all(isinstance(s, (list, tuple)) for s in seed):
+        if any(len(s) != V for s in seed):
+            raise ValueError("seed= holds %s seeds per image for variations=%d" % ([len(s) for s in seed], V))
+        seed = [v for s in seed for v in s]
     seed = [int(s) for s in seed]
-    if len(seed) != B:
-        raise ValueError("seed= holds %d seeds for a batch of %d (one int, or one per image)" % (len(seed), B))
+    if len(seed) != B * V:
+        raise ValueError("seed= holds %d seeds for a batch of %d (one int, or one per image)" % (len(seed), B * V)
+                         + (" = %d images x %d variations (nested [B][V], or flat in output order)" % (B, V) if V > 1 else ""))
     return seed
 
 
@@ -401,6 +417,14 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         if weights.meta.get("rank_unet"):
             self.lora_rank_unet, self.lora_rank_vae = weights.meta["rank_unet"], weights.meta["rank_vae"]
 
+    def get_plan(self, B, H, W, *args, variations=1, **kw) -> ForwardPlan:
+        """TurboGeneratorBase.get_plan with ``variations=V`` (part of the LRU key; 1 = the key and the plan of a call without it): V outputs per
+        input image from one pass of the input ops and the VAE encoder (ForwardPlan(variations=V)) -- "x" holds B images, "eps" / "noise" /
+        the seed rows / "out" B * V, output slot b * V + v."""
+        if int(variations) < 1:
+            raise ValueError("variations=%r (an integer >= 1)" % (variations,))
+        return super().get_plan(B, H, W, *args, _variations=int(variations), **kw)
+
     @torch.no_grad()
     def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, return_edges=False, resample="lanczos", **kw):
         """uint8 HWC in, uint8 HWC out ([B, H, W, 3] on the device): the callers' ``F.to_tensor`` (src/inference_paired.py:50)
@@ -424,7 +448,8 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         edges, thr)``, thr int32 [B, 2] the {low, high} pairs that were used.
         ``resample="bicubic"``: the resize uses Pillow's BICUBIC tables, bit-identical to ``Image.resize(size)`` with no filter argument
         (gradio_canny2image.py:16); the default is the scripts' LANCZOS.
-        ``seed=``: as in ``forward``.
+        ``seed=`` / ``variations=``: as in ``forward``; with ``canny=`` the edges are computed once per input and ``return_edges=True`` returns
+        the B maps (not B * V).
         ``images_u8`` may also be a LIST of uint8 [H_b, W_b, 3] tensors of different sizes with ``resize=(width, height)``: the requests of a
         batch are brought to the model size in two launches (image_ops.lanczos_resize_u8_ragged) and image b of the result is what the
         stacked, pre-resized batch gives.  A list needs an explicit size: ``resize=None`` / ``"multiple_of_8"`` would leave the images at
@@ -456,17 +481,24 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
 
     @torch.no_grad()
     def forward(self, c_t, prompt=None, prompt_tokens=None, deterministic=True, r=1.0, noise_map=None,
-                *, caption_enc=None, eps=None, seed=None, _u8_io=None, _canny=None):
+                *, caption_enc=None, eps=None, seed=None, variations=1, _u8_io=None, _canny=None):
         """``seed=s``: the scripts' ``torch.manual_seed(s)`` + ``torch.randn`` (src/inference_paired.py:58-60) on the device -- the planned
         program draws "eps" (and, stochastic, the noise map) itself at (seed s, step 0) under the contract of i2i_randn_params
         (include/i2i_turbo.h; img2img_turbo_amd.rng): nothing is staged by the host, the same seed gives the same image on every call, and
         ``noise_map`` is not needed.  Not together with ``eps=`` / ``noise_map=``.  ``seed=None``: as before.
         ``seed=[s0, .., sB-1]``: one seed per image, every image at step 0 (the contract of i2i_randn_batch_params): image b's noise is what
         a batch-1 call with ``seed=sb`` draws, whatever its slot -- the noise, not necessarily every bit of the image (the kernels choose
-        their routes by batch size)."""
+        their routes by batch size).
+        ``variations=V``: V outputs per input image -- the seed gallery of gradio_sketch2image.py ("try different seeds to generate
+        different results") in one call.  Returns B * V images, image-major (slot b * V + v); the input ops and the VAE encoder run once per
+        INPUT (nothing in front of the posterior sample depends on the seed).  ``seed``: one int, a nested [B][V] list or a flat list of
+        B * V; explicit ``eps`` / ``noise_map`` have leading dimension B * V; ``caption_enc`` [1 | B | B * V, 77, D]."""
+        V = int(variations)
+        if V < 1:
+            raise ValueError("variations=%r (an integer >= 1)" % (variations,))
         if seed is not None and (eps is not None or noise_map is not None):
             raise ValueError("seed= draws eps and the noise map on the device: do not pass eps= / noise_map= with it")
-        seed = seed_argument(seed, c_t.shape[0])
+        seed = seed_argument(seed, c_t.shape[0], V)
         if caption_enc is None:
             # either the prompt or the prompt_tokens should be provided (src/pix2pix_turbo.py:188)
             assert (prompt is None) != (prompt_tokens is None), "Either prompt or prompt_tokens should be provided"
@@ -483,12 +515,16 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
                              "deterministic=False (TwinConv.r is None otherwise, src/pix2pix_turbo.py:21-26)")
         lat = self.weights.vae_arch.latent_channels
         if eps is None and seed is None:   # latent_dist.sample() draw, then the (numerically dead) scheduler draw: same order as the reference
-            eps = torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
-            torch.randn(B, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
+            eps = torch.randn(B * V, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
+            torch.randn(B * V, lat, H // 8, W // 8, device=self.device_, dtype=torch.float32)
         ctx_batch = caption_enc.shape[0] if caption_enc.dim() == 3 else 1
-        assert ctx_batch in (1, B)
+        assert ctx_batch in (1, B, B * V)
+        if V > 1:
+            for name, t in (("eps", eps), ("noise_map", noise_map)):
+                if t is not None and t.shape[0] != B * V:
+                    raise ValueError("%s holds %d images for %d images x %d variations (leading dimension B * V)" % (name, t.shape[0], B, V))
         plan = self.get_plan(B, H, W, stochastic=not deterministic, r=r, ctx_batch=ctx_batch, u8_io=_u8_io, canny=per_image_mode(_canny),
-                             rng=("per_image" if isinstance(seed, list) else seed is not None))
+                             rng=("per_image" if isinstance(seed, list) else seed is not None), variations=V)
         out = self._execute(plan, c_t, caption_enc, eps, None if deterministic else noise_map, canny=_canny, seed=seed)
         if _u8_io is not None:
             return out

@@ -86,11 +86,23 @@ class ForwardPlan:
 
     def __init__(self, lib, weights, B, H, W, dtype, device, *, stochastic=False, r=1.0, direction="a2b",
                  ctx_batch=1, fuse_gn=True, flash=True, out_dtype=None, packers=None, debug=False, dma_small=True, fuse_gn_stats=True, subpix=True, halo_min_tiles=160, u8_io=None, fuse_vae_attention=True,
-                 unet_dtype=None, canny=False, rng=False, health=None, health_limit=None, health_per_image=False, fingerprint=None):
+                 unet_dtype=None, canny=False, rng=False, health=None, health_limit=None, health_per_image=False, fingerprint=None, variations=1):
         assert H % 8 == 0 and W % 8 == 0, "input must be a multiple of 8 (src/inference_paired.py:38-41)"
         # H, W multiples of 8 suffice (src/inference_paired.py:38-41): latent sizes that are not multiples of 8 make the
         # UNet levels odd (70 -> 35 -> 18 -> 9), handled like diffusers' forward_upsample_size path (explicit sizes).
         self.lib, self.w8s, self.B, self.H, self.W = lib, weights, B, H, W
+        # variations = V: V outputs per input image from ONE pass of the input ops and the VAE encoder -- nothing in front of the posterior
+        # sample depends on the seed (src/pix2pix_turbo.py:197-198).  The input ops and the encoder are built at batch B (x_in and the Canny
+        # buffers hold B images), one I2I_OP_REPEAT (the contract of i2i_repeat_params) writes the moments and the encoder skips at batch
+        # B * V, image-major (output slot b * V + v), and from posterior_sample on the program is the ordinary one at batch B * V: eps, noise,
+        # rng_state and out hold B * V images.  variations = 1 records exactly the program it always did (no repeat op).
+        self.V = int(variations)
+        assert self.V >= 1, "variations must be >= 1"
+        self.BV = B * self.V
+        self._nb = B            # images of the tensors the builder is recording right now (B in front of the repeat, B * V behind it)
+        if self.V > 1 and health_per_image:
+            raise ValueError("health_per_image=True with variations=%d: per-image health of a variations plan is not supported (B inputs, "
+                             "B * V outputs: the verdict rows have no mapping between them); use whole-batch health" % self.V)
         self.dtype, self.device = dtype, device
         self.dt = O.DT[dtype]
         # Per-network precision: `dtype` is the VAE's (activations, packed weights), `unet_dtype` the UNet's (default: the same).  The two
@@ -143,6 +155,7 @@ class ForwardPlan:
         assert fingerprint in (None, "io", "stages", "all"), fingerprint
         self.fingerprint_mode = fingerprint
         self.fingerprint_labels, self.fingerprint_rec, self._fp_ops, self._fp_clear = [], None, [], None
+        self._fp_images = []      # images of tap i: B everywhere, except behind the repeat op of a variations plan (B * V)
         self.prog = K.Program()
         self.op_flops = []      # algorithmic FLOPs per op (2*MAC), parallel to prog.ops
         self.op_flops_exec = [] # FLOPs the matrix pipe executes for the op (sub-pixel upsamplers: 4/9 of the 3x3 part), parallel to prog.ops
@@ -189,6 +202,12 @@ class ForwardPlan:
         # u8_io = (mul, add) of the input normalisation: the boundary becomes uint8 HWC image batches on both sides
         # (row f1: F.to_tensor / Normalize / x*0.5+0.5 / ToPILImage of the callers run inside the boundary kernels)
         self.u8_io = u8_io
+        # (a caption per INPUT image of a variations plan, ctx_batch == B: the buffer holds B * V rows, image-major, and the owner expands
+        # the B captions when it stages them -- the attention kernels then see an ordinary per-image context)
+        assert ctx_batch in (1, B, self.BV), "ctx_batch must be 1, B or B * variations"
+        self.ctx_in_batch = ctx_batch
+        if ctx_batch > 1:
+            ctx_batch = self.BV
         self.ctx_batch = ctx_batch
         # canny: the program starts with Canny edge detection of x_in (the edge_to_image script's canny_from_pil, src/inference_paired.py:47-50;
         # csrc/resize.hip): x_in holds the photos, the boundary op reads the plan-owned edge maps.  The thresholds are DEVICE state
@@ -215,8 +234,9 @@ class ForwardPlan:
             self.canny_auto_ws = torch.zeros(max(lib.canny_auto_ws_bytes(B), 16), dtype=torch.uint8, device=device)
         self.x_in = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
                      torch.zeros(B, 3, H, W, dtype=torch.float32, device=device))
-        self.eps = torch.zeros(B, lat, h8, w8, dtype=torch.float32, device=device)
-        self.noise = torch.zeros(B, lat, h8, w8, dtype=torch.float32, device=device) if stochastic else None
+        BV = self.BV
+        self.eps = torch.zeros(BV, lat, h8, w8, dtype=torch.float32, device=device)
+        self.noise = torch.zeros(BV, lat, h8, w8, dtype=torch.float32, device=device) if stochastic else None
         # rng: the program fills eps (and noise) itself -- seeded noise under the contract of i2i_randn_params (include/i2i_turbo.h), streams 0 and
         # 2 -- from the DEVICE state rng_state = {seed_lo, seed_hi, step, reserved} (uint32 bits in an int32 tensor), and ends by advancing
         # the step: the callers' torch.manual_seed(seed) + torch.randn (src/inference_paired.py:58-60) with one program, one hipGraph and one
@@ -226,10 +246,10 @@ class ForwardPlan:
         assert rng in (False, True, "per_image"), rng
         self.rng = rng if rng == "per_image" else bool(rng)
         self.rng_per_image = rng == "per_image"
-        self.rng_state = torch.zeros((B, 4) if self.rng_per_image else 4, dtype=torch.int32, device=device) if self.rng else None
+        self.rng_state = torch.zeros((BV, 4) if self.rng_per_image else 4, dtype=torch.int32, device=device) if self.rng else None
         self.ctx = torch.zeros(ctx_batch, 77, self.ua.cross_attention_dim, dtype=self.unet_dtype, device=device)
-        self.out = (torch.zeros(B, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
-                    torch.zeros(B, 3, H, W, dtype=self.out_dtype, device=device))
+        self.out = (torch.zeros(BV, H, W, 3, dtype=torch.uint8, device=device) if u8_io else
+                    torch.zeros(BV, 3, H, W, dtype=self.out_dtype, device=device))
         if self.health_per_image:
             self._verdict_ops = [O.scan_verdict(None, None, taps=0, images=B, mode=K.VERDICT_CLEAR),
                                  O.scan_verdict(None, None, taps=0, images=B, mode=K.VERDICT_JUDGE)]
@@ -239,12 +259,12 @@ class ForwardPlan:
             self._add(self._fp_clear, "fingerprint: clear", kernel="digest_clear")
         self._build()
         if self.fingerprint_mode == "io":
-            self._fp("x", self.x_in, B, self.x_in.numel() // B)
+            self._fp("x", self.x_in, B, self.x_in.numel() // B, images=B)
             self._fp("ctx", self.ctx, ctx_batch, self.ctx.numel() // ctx_batch, images=ctx_batch)
-            self._fp("eps", self.eps, B, self.eps.numel() // B)
+            self._fp("eps", self.eps, BV, self.eps.numel() // BV, images=BV)
             if self.noise is not None:
-                self._fp("noise", self.noise, B, self.noise.numel() // B)
-            self._fp("out", self.out, B, self.out.numel() // B)
+                self._fp("noise", self.noise, BV, self.noise.numel() // BV, images=BV)
+            self._fp("out", self.out, BV, self.out.numel() // BV, images=BV)
         if self.health_per_image:
             self._add(self._verdict_ops[1], "health: verdict", kernel="scan_verdict")
         self._finish_gn_scratch()
@@ -346,7 +366,7 @@ class ForwardPlan:
         """Record one digest of the rows x cols view of tensor ``t`` (batch-outermost: image b is rows / images consecutive rows), one record
         per image; the record pointer is patched in _finish_fingerprint."""
         from .digest import dtype_code
-        images = self.B if images is None else images
+        images = self._nb if images is None else images      # (a variations plan: B in front of the repeat op, B * V behind it)
         assert rows % images == 0, "tap %s is not batch-outermost: %d rows for %d images" % (label, rows, images)
         op = O.digest(t, None, images=images, rows=rows // images, cols=cols, ld=ld)
         old = self.dt
@@ -356,29 +376,32 @@ class ForwardPlan:
         finally:
             self.dt = old
         self._fp_ops.append(op[1])
+        self._fp_images.append(images)
         self.fingerprint_labels.append(label)
 
     def _finish_fingerprint(self):
         if not self.fingerprint_mode:
             return
-        n = len(self._fp_ops)
-        self._fp_i64 = torch.zeros(max(n, 1) * self.B, 4, dtype=torch.int64, device=self.device)      # (the kernel sees uint64)
-        self.fingerprint_rec = self._fp_i64.view(torch.uint64)[:n * self.B].view(n, self.B, 4)
+        n, per = len(self._fp_ops), self.BV       # records per tap: a tap of B images of a variations plan leaves the rows from B on zero
+        self._fp_i64 = torch.zeros(max(n, 1) * per, 4, dtype=torch.int64, device=self.device)      # (the kernel sees uint64)
+        self.fingerprint_rec = self._fp_i64.view(torch.uint64)[:n * per].view(n, per, 4)
         for i, p in enumerate(self._fp_ops):
-            p.rec = self._fp_i64.data_ptr() + 32 * self.B * i
+            p.rec = self._fp_i64.data_ptr() + 32 * per * i
             p._keep = tuple(p._keep) + (self._fp_i64,)
         clear = self._fp_clear[1]
-        clear.rec, clear.n_records, clear._keep = self._fp_i64.data_ptr(), n * self.B, (self._fp_i64,)
+        clear.rec, clear.n_records, clear._keep = self._fp_i64.data_ptr(), n * per, (self._fp_i64,)
         self.fingerprint_names = torch.tensor(list(b"".join(l.encode() + b"\0" for l in self.fingerprint_labels)) or [0], dtype=torch.uint8, device=self.device)
 
     def fingerprint(self):
         """Synchronise and return [(label, uint64 [B, 4])] of the most recent run or replay, in program order: {s0, s1, elements, 0} per image
-        (the contract of i2i_digest_params).  Compare two of them with digest.first_diff."""
+        (the contract of i2i_digest_params).  Compare two of them with digest.first_diff.  On a variations plan the taps up to and including
+        "moments" (and "x" of the io mode) carry B rows, the later ones B * V."""
         assert self.fingerprint_mode, "this plan has no fingerprints (ForwardPlan(fingerprint=...))"
         if torch.device(self.device).type == "cuda":
             torch.cuda.synchronize(self.device)
-        rec = self._fp_i64.cpu().view(torch.uint64)[:len(self.fingerprint_labels) * self.B].view(len(self.fingerprint_labels), self.B, 4)
-        return [(label, rec[i].clone()) for i, label in enumerate(self.fingerprint_labels)]
+        rec = self._fp_i64.cpu().view(torch.uint64)[:len(self.fingerprint_labels) * self.BV].view(len(self.fingerprint_labels), self.BV, 4)
+        # (a tap of B images returns B rows, every other one B * V -- a shared context among them: image 0's record, the others zero)
+        return [(label, rec[i, :(self.B if self._fp_images[i] == self.B else self.BV)].clone()) for i, label in enumerate(self.fingerprint_labels)]
 
     def health_reset(self):
         """Zero every record, and on a per-image plan the verdict rows (fills on the current stream; asynchronous)."""
@@ -1209,6 +1232,19 @@ class ForwardPlan:
         self._stage("pre_clamp", y, cols=3)
         return y
 
+    def _repeat(self, moments: Act, skips: List[Act]):
+        """The broadcast of a variations plan: ONE launch (I2I_OP_REPEAT, the contract of i2i_repeat_params) copies the posterior moments and
+        the encoder skips of every input image to its V output slots, image-major.  The B-sized tensors go back to the pool: the ops behind
+        see ordinary tensors of batch B * V."""
+        srcs = [moments] + list(skips)
+        dsts = [Act(self.pool.get(self.V * a.t.numel(), a.t.dtype), a.n * self.V, a.h, a.w, a.c) for a in srcs]
+        nbytes = sum(a.t.numel() * a.t.element_size() for a in srcs)
+        self._add(O.repeat([(a.t, d.t) for a, d in zip(srcs, dsts)], batch=self.B, variations=self.V), "variations.repeat", kernel="repeat_kernel",
+                  nbytes=nbytes * (1 + self.V))
+        for a in srcs:
+            self.free(a)
+        return dsts[0], dsts[1:]
+
     def _build(self):
         B, H, W = self.B, self.H, self.W
         lat = self.va.latent_channels
@@ -1218,9 +1254,9 @@ class ForwardPlan:
         mul, add, thr = (tuple(self.u8_io) + (0,))[:3] if self.u8_io else (1.0, 0.0, 0)      # (mul, add[, binarize_below])
         if self.rng_per_image:
             from .rng import STREAM_EPS, STREAM_NOISE
-            self._add(O.randn_batch(self.eps, self.rng_state, batch=B, stream_id=STREAM_EPS), "rng.eps", nbytes=self.eps.numel() * 4)
+            self._add(O.randn_batch(self.eps, self.rng_state, batch=self.BV, stream_id=STREAM_EPS), "rng.eps", nbytes=self.eps.numel() * 4)
             if self.noise is not None:
-                self._add(O.randn_batch(self.noise, self.rng_state, batch=B, stream_id=STREAM_NOISE), "rng.noise", nbytes=self.noise.numel() * 4)
+                self._add(O.randn_batch(self.noise, self.rng_state, batch=self.BV, stream_id=STREAM_NOISE), "rng.noise", nbytes=self.noise.numel() * 4)
         elif self.rng:
             from .rng import STREAM_EPS, STREAM_NOISE
             self._add(O.randn(self.eps, state=self.rng_state, stream_id=STREAM_EPS), "rng.eps", nbytes=self.eps.numel() * 4)
@@ -1243,6 +1279,9 @@ class ForwardPlan:
         moments, skips = self._vae_encoder(x)
         # x (= conv_in input) is not a skip; skips[0] is conv_in's output
         self.free(x)
+        if self.V > 1:        # everything below is the ordinary program at batch B * V
+            moments, skips = self._repeat(moments, skips)
+            B = self._nb = self.BV
         self.u32 = torch.zeros(B * h8 * w8 * lat, dtype=torch.float32, device=self.device)
         sf = self.va.scaling_factor
         with self._as(self.unet_dtype):          # fp32 moments in, the UNet's element type out; eps-prediction comes back in fp32
@@ -1266,7 +1305,7 @@ class ForwardPlan:
         self._add(O.nhwc_to_nchw(y.t, self.out, n=B, c=3, h=H, w=W, ldx=y.c, clamp=1, mul=0.5, add=0.5), "output.from_nhwc",
                   nbytes=B * H * W * (y.c * self.esz + 3 * self.out.element_size()))
         if self.rng_per_image:
-            self._add(O.randn_batch(None, self.rng_state, batch=B, kind=K.RANDN_ADVANCE), "rng.advance")
+            self._add(O.randn_batch(None, self.rng_state, batch=self.BV, kind=K.RANDN_ADVANCE), "rng.advance")
         elif self.rng:        # last: every fill of one run saw the same step
             self._add(O.randn(None, state=self.rng_state, kind=K.RANDN_ADVANCE), "rng.advance")
         for t in self._zero_init:
@@ -1337,14 +1376,19 @@ class ForwardPlan:
             self.rng_state[i:i + 1].fill_(as_i32(word))          # (fill kernels, as set_canny_thresholds)
 
     def set_seeds(self, seeds, steps=0):
-        """Per-image plans (rng="per_image"): write the noise state row of every image -- ``seeds``: B ints (each reduced mod 2^64),
+        """Per-image plans (rng="per_image"): write the noise state row of every image -- ``seeds``: B ints (each reduced mod 2^64; on a
+        variations plan B * V ints in output order, slot b * V + v, or a nested [B][V] list),
         ``steps``: one int or B ints.  Every run advances every row's step by one.  Asynchronous on the current stream; the values travel as
         launch arguments of fill kernels, so no host buffer has to outlive the call."""
         assert self.rng_per_image, "this plan holds one noise state for the batch: use set_seed (or get_plan(..., rng=\"per_image\"))"
         from .rng import as_i32, pack_states
         seeds = list(seeds)
-        if len(seeds) != self.B:
-            raise ValueError("%d seeds for a batch of %d" % (len(seeds), self.B))
+        if self.V > 1 and len(seeds) == self.B and all(isinstance(s, (list, tuple)) for s in seeds):      # [B][V] -> slot b * V + v
+            if any(len(s) != self.V for s in seeds):
+                raise ValueError("seeds: %s seeds per image for %d variations" % ([len(s) for s in seeds], self.V))
+            seeds = [v for s in seeds for v in s]
+        if len(seeds) != self.BV:
+            raise ValueError("%d seeds for a batch of %d" % (len(seeds), self.BV) + (" (%d images x %d variations)" % (self.B, self.V) if self.V > 1 else ""))
         rows = pack_states(seeds, steps)
         same_step = isinstance(steps, int)          # (the common call: one strided fill for the step column, one for the reserved word)
         for b, row in enumerate(rows):

@@ -58,7 +58,8 @@ _WRITES = {K.OP_IGEMM: ("c", "c2", "ws", "gn_part"), K.OP_GN_STATS: ("partial", 
            K.OP_DDPM_POSTQUANT: ("y",), K.OP_EMBED: ("y",), K.OP_LORA_MERGE: ("dst", "colsum", "bias_out"), K.OP_RESIZE_U8: ("dst",), K.OP_NOP: (),
            K.OP_CANNY_U8: ("dst", "ws"), K.OP_RANDN: ("dst", "state"), K.OP_TWIN_FOLD: ("dst", "bias"), K.OP_SCAN: ("rec",),
            K.OP_RANDN_BATCH: ("dst", "states"), K.OP_CANNY_U8_BATCH: ("dst", "ws"), K.OP_RESIZE_U8_RAGGED: ("dst", "bad_mask"),
-           K.OP_SCAN_BATCH: ("rec",), K.OP_SCAN_VERDICT: ("rec", "verdict"), K.OP_CANNY_AUTO_THR: ("thr", "median2", "ws"), K.OP_DIGEST: ("rec",)}
+           K.OP_SCAN_BATCH: ("rec",), K.OP_SCAN_VERDICT: ("rec", "verdict"), K.OP_CANNY_AUTO_THR: ("thr", "median2", "ws"), K.OP_DIGEST: ("rec",),
+           K.OP_REPEAT: tuple("dst%d" % s for s in range(K.REPEAT_MAX_SEGMENTS))}
 
 
 def _pointer_fields():
@@ -267,7 +268,7 @@ def export_program(prog, path, named, scratch=(), holders=(), device="cpu", keep
 
 def main(argv=None):
     """python -m img2img_turbo_amd.plan_file --out pix2pix_bs8_512.i2iplan [--model pix2pix|cyclegan] [--batch 8 --size 512 --dtype bf16]
-    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH | --canny-auto SIGMA]] [--seed N | --seeds S0,S1,..] [--health stages|all [--health-per-image]] [--fingerprint io|stages|all] [--digests] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
+    [--stochastic --gamma 0.4] [--live-scale] [--direction a2b] [--u8 [--canny LOW HIGH | --canny-per-image LOW HIGH | --canny-auto SIGMA]] [--seed N | --seeds S0,S1,..] [--variations V] [--health stages|all [--health-per-image]] [--fingerprint io|stages|all] [--digests] (--base-dir <sd-turbo snapshot> --pretrained-path <lora .pkl> | --synthetic)"""
     import argparse
     ap = argparse.ArgumentParser(description="export a planned forward to a plan file for C / C++ hosts (include/i2i_turbo.h i2i_plan_*)")
     ap.add_argument("--out", required=True)
@@ -291,6 +292,9 @@ def main(argv=None):
     ap.add_argument("--seeds", default=None, metavar="S0,S1,..", help="--batch comma-separated seeds: as --seed with ONE noise state per image "
                     "(i2i_randn_batch_params: image b's noise does not depend on its slot); 'seed' is then 16 bytes per image, row b = {seed_lo, "
                     "seed_hi, step, 0} of image b")
+    ap.add_argument("--variations", type=int, default=1, metavar="V", help="pix2pix: V outputs per input image from one pass of the input ops and the "
+                    "VAE encoder (ForwardPlan(variations=V), i2i_repeat_params): 'x' holds --batch images, 'eps' / 'noise' / 'out' and the rows of "
+                    "'seed' (--seeds then takes batch * V values) batch * V, output slot b * V + v")
     ap.add_argument("--canny-per-image", type=float, nargs=2, default=None, metavar=("LOW", "HIGH"), help="as --canny with one {low, high} pair per "
                     "image: 'canny_thr' is 8 bytes per image, every row saved as LOW HIGH")
     ap.add_argument("--canny-auto", type=float, default=None, metavar="SIGMA", help="as --canny-per-image, with the thresholds computed by the program "
@@ -327,14 +331,18 @@ def main(argv=None):
         a.canny = a.canny_per_image
     if a.seed is not None and a.seeds is not None:
         ap.error("--seed and --seeds are exclusive")
+    if a.variations < 1:
+        ap.error("--variations takes an integer >= 1")
+    if a.variations > 1 and (a.model != "pix2pix" or a.health_per_image):
+        ap.error("--variations is a pix2pix option, and not available with --health-per-image")
     seeds = None
     if a.seeds is not None:
         try:
             seeds = [int(s, 0) for s in a.seeds.split(",")]
         except ValueError:
             ap.error("--seeds takes comma-separated integers")
-        if len(seeds) != a.batch:
-            ap.error("--seeds holds %d values for --batch %d" % (len(seeds), a.batch))
+        if len(seeds) != a.batch * max(a.variations, 1):
+            ap.error("--seeds holds %d values for --batch %d" % (len(seeds), a.batch) + (" x --variations %d" % a.variations if a.variations > 1 else ""))
     rng_mode = "per_image" if seeds is not None else (a.seed is not None)
     if (a.canny is not None or a.canny_auto is not None) and (not a.u8 or a.model != "pix2pix" or a.sketch or a.stochastic):
         ap.error("--canny requires --u8 on a deterministic pix2pix plan (the edge_to_image branch; not with --sketch / --stochastic)")
@@ -365,7 +373,7 @@ def main(argv=None):
         # `F.to_tensor(img) < 0.5`), which is what Pix2Pix_Turbo.forward_u8(..., sketch=True) feeds -- a stochastic plan is the sketch model
         u8 = ((1.0, 0.0, 128) if (a.sketch or a.stochastic) else (1.0, 0.0)) if a.u8 else None
         gamma = a.gamma if a.gamma is not None else (0.4 if a.stochastic else 1.0)
-        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=canny_mode, rng=rng_mode)
+        plan = model.get_plan(a.batch, H, W, stochastic=a.stochastic, r=gamma, u8_io=u8, canny=canny_mode, rng=rng_mode, variations=a.variations)
         if a.canny is not None:
             plan.set_canny_thresholds(*a.canny)
         if a.canny_auto is not None:

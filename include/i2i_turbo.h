@@ -64,7 +64,8 @@ typedef enum {
     I2I_OP_SCAN_BATCH = 22,        /* ABI 14 additions (see the note above i2i_scan_batch_params) */
     I2I_OP_SCAN_VERDICT = 23,
     I2I_OP_CANNY_AUTO_THR = 24,    /* ABI 14 addition (see the note above i2i_canny_auto_thr_params) */
-    I2I_OP_DIGEST = 25             /* ABI 14 addition (see the note above i2i_digest_params) */
+    I2I_OP_DIGEST = 25,            /* ABI 14 addition (see the note above i2i_digest_params) */
+    I2I_OP_REPEAT = 26             /* ABI 14 addition (see the note above i2i_repeat_params) */
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -632,6 +633,48 @@ typedef struct {
     int64_t n_records;                 /* I2I_DIGEST_CLEAR: records to zero */
 } i2i_digest_params;
 
+/* ---- ABI 14 addition: variations, one input image -> V outputs (I2I_OP_REPEAT).  Purely additive like the ones above -- one new opcode, two
+ * new structs, one new exported function; no existing struct, opcode number or signature changed and sizeof(i2i_op) did not grow (208 bytes
+ * inside the union i2i_igemm_params sizes) -- so I2I_ABI_VERSION stays 14.  A library built before the addition is recognised by the missing
+ * symbol (i2i_repeat), and its plan loader refuses the new opcode as unknown.
+ *
+ * torch.repeat_interleave(x, V, dim = 0) of up to I2I_REPEAT_MAX_SEGMENTS batch-outermost tensors ("segments") in ONE launch: the broadcast
+ * from B encoded inputs to B * V generator inputs of ForwardPlan(variations = V) -- the posterior moments and the four encoder skips, which
+ * do not depend on the seed (src/pix2pix_turbo.py:197-198: the seed enters at latent_dist.sample()), so the VAE encoder runs once per input
+ * ("try different seeds to generate different results", gradio_sketch2image.py) and everything behind this op is the ordinary program at
+ * batch B * V.
+ *   LAYOUT     segment s is `batch` images of bytes_per_image bytes each, contiguous, at src; dst holds batch * variations such images.
+ *              Bytes, not elements: the op does not look at the element type (the op's dtype is ignored), segments of one launch may differ.
+ *   ORDER      IMAGE-MAJOR:  dst[(b * variations + v) * n + i] = src[b * n + i]   for b < batch, v < variations, i < n = bytes_per_image:
+ *              the variations of input b are the consecutive output slots b * V .. b * V + V - 1.
+ *   ALIGNMENT  bytes_per_image is a multiple of 16 and src / dst are 16-byte aligned (NHWC activations with C padded to 8 and the fp32
+ *              moments are); bytes_per_image < 2^35.  bytes_per_image == 0 is an empty segment: nothing of it is read or written (src / dst
+ *              must still be given).
+ *   TABLE      the segments travel BY VALUE inside this struct -- in an i2i_op of a program, a captured graph or a plan file, and from there in
+ *              the kernel-argument segment of the launch, which is how the device sees them: no device-side table to allocate, upload or
+ *              keep alive, and the plan loader relocates seg[s].src / seg[s].dst like any other pointer field.
+ *   READ ONCE  every 16-byte vector of a source is loaded ONCE and stored `variations` times (dwordx4 both ways): the traffic is (1 + V) / V
+ *              bytes per output byte, not 2.  src and dst must not overlap; segments must not overlap in dst.
+ * One launch: a 1-D grid over the 16-byte vectors of all segments together, 1024 vectors per workgroup; a workgroup finds its segment from a
+ * prefix array of workgroup counts by blockIdx alone (wave-uniform, as i2i_merge_group_run does).  All offsets are 64-bit (64 images of a
+ * 128-channel 512 x 512 skip are 4 GiB).  No LDS, no atomics, no allocation, no synchronisation; graph-capturable; runs on the caller's stream.
+ * batch == 0 or n_segments == 0 is a successful no-op.
+ * Errors (I2I_ERR_BAD_ARG, nothing written; the message names the field): null params; variations < 1; batch < 0; n_segments outside
+ * 0 .. I2I_REPEAT_MAX_SEGMENTS; a segment's bytes_per_image negative, not a multiple of 16 or >= 2^35; its src or dst null or not 16-byte
+ * aligned; sizes whose product leaves 2^61 or a grid past 2^31 - 1 workgroups. */
+#define I2I_REPEAT_MAX_SEGMENTS 8
+typedef struct {
+    const void* src;                   /* [batch][bytes_per_image] */
+    void* dst;                         /* [batch * variations][bytes_per_image] */
+    int64_t bytes_per_image;           /* multiple of 16 */
+} i2i_repeat_segment;
+typedef struct {
+    int32_t batch, variations;         /* B >= 0, V >= 1 */
+    int32_t n_segments;                /* 0 .. I2I_REPEAT_MAX_SEGMENTS */
+    int32_t reserved;                  /* ignored */
+    i2i_repeat_segment seg[I2I_REPEAT_MAX_SEGMENTS];      /* entries from n_segments on are ignored (keep them zero in a plan file) */
+} i2i_repeat_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -663,6 +706,7 @@ typedef struct {
         i2i_scan_verdict_params scan_verdict;
         i2i_canny_auto_thr_params canny_auto_thr;
         i2i_digest_params digest;
+        i2i_repeat_params repeat;
     } u;
 } i2i_op;
 
@@ -707,6 +751,7 @@ int i2i_scan_verdict(const i2i_scan_verdict_params* p, int dtype, void* stream);
 int i2i_canny_auto_thr(const i2i_canny_auto_thr_params* p, int dtype, void* stream);   /* dtype ignored (uint8 data); three launches */
 size_t i2i_canny_auto_ws_bytes(int n);                                                 /* bytes of i2i_canny_auto_thr_params.ws (0 for n < 1) */
 int i2i_digest(const i2i_digest_params* p, int dtype, void* stream);                   /* one launch; dtype = element type of x (I2I_U8 allowed) */
+int i2i_repeat(const i2i_repeat_params* p, int dtype, void* stream);                   /* dtype ignored (bytes); one launch */
 /* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
  * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
  * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
