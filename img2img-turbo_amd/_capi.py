@@ -28,6 +28,7 @@ OP_SCAN_BATCH, OP_SCAN_VERDICT = 22, 23      # per-image health (i2i_scan_batch_
 OP_CANNY_AUTO_THR = 24                      # automatic per-image Canny thresholds (i2i_canny_auto_thr_params)
 OP_DIGEST = 25                              # device fingerprints (i2i_digest_params)
 OP_REPEAT = 26                              # variations: image-major replication of up to 8 tensors (i2i_repeat_params)
+OP_TILE_CUT, OP_TILE_BLEND_U8 = 27, 28          # tiled forward: cut requests into tiles, feather-blend the tile outputs (i2i_tile_request)
 REPEAT_MAX_SEGMENTS = 8
 DIGEST_ADD, DIGEST_CLEAR = 0, 1             # i2i_digest_kind
 ERR_UNSUPPORTED, ERR_MISMATCH = -3, -5      # i2i_status values callers tell apart (i2i_plan_verify)
@@ -181,6 +182,21 @@ class RepeatParams(C.Structure):
                 + [f for s in range(REPEAT_MAX_SEGMENTS) for f in (("src%d" % s, vp), ("dst%d" % s, vp), ("bytes%d" % s, i64))])
 
 
+class TileRequest(C.Structure):
+    """One request of a tiled forward (i2i_tile_request, 48 bytes, lives in DEVICE memory: image_ops.TILE_REQUEST_DTYPE packs it)."""
+    _fields_ = [("off", i64), ("h", i32), ("w", i32), ("tile0", i32), ("nx", i32), ("ny", i32), ("xs_off", i32), ("ys_off", i32), ("reserved", i32 * 3)]
+
+
+class TileCutParams(C.Structure):
+    _fields_ = [("src", vp), ("dst", vp), ("arena_bytes", i64), ("reqs", vp), ("pos", vp), ("pos_len", i64), ("n", i32), ("planes", i32),
+                ("px_bytes", i32), ("tw", i32), ("th", i32), ("tiles_capacity", i32), ("grid_units", i64), ("bad_mask", vp)]
+
+
+class TileBlendU8Params(C.Structure):
+    _fields_ = [("tiles", vp), ("dst", vp), ("arena_bytes", i64), ("reqs", vp), ("pos", vp), ("pos_len", i64), ("n", i32), ("c", i32),
+                ("ramp", i32), ("tw", i32), ("th", i32), ("tiles_capacity", i32), ("grid_units", i64), ("bad_mask", vp)]
+
+
 class NopParams(C.Structure):
     _fields_ = [("unused", i32)]
 
@@ -193,7 +209,7 @@ class _OpUnion(C.Union):
                 ("nop", NopParams), ("canny_u8", CannyU8Params), ("randn", RandnParams), ("twin_fold", TwinFoldParams), ("scan", ScanParams),
                 ("randn_batch", RandnBatchParams), ("canny_u8_batch", CannyU8BatchParams), ("resize_u8_ragged", ResizeU8RaggedParams),
                 ("scan_batch", ScanBatchParams), ("scan_verdict", ScanVerdictParams), ("canny_auto_thr", CannyAutoThrParams),
-                ("digest", DigestParams), ("repeat", RepeatParams)]
+                ("digest", DigestParams), ("repeat", RepeatParams), ("tile_cut", TileCutParams), ("tile_blend_u8", TileBlendU8Params)]
 
 
 class Op(C.Structure):
@@ -206,7 +222,7 @@ _FIELD_OF = {OP_IGEMM: "igemm", OP_GN_STATS: "gn_stats", OP_GN_APPLY: "gn_apply"
              OP_LORA_MERGE: "lora_merge", OP_RESIZE_U8: "resize_u8", OP_NOP: "nop", OP_CANNY_U8: "canny_u8", OP_RANDN: "randn", OP_TWIN_FOLD: "twin_fold", OP_SCAN: "scan",
              OP_RANDN_BATCH: "randn_batch", OP_CANNY_U8_BATCH: "canny_u8_batch", OP_RESIZE_U8_RAGGED: "resize_u8_ragged",
              OP_SCAN_BATCH: "scan_batch", OP_SCAN_VERDICT: "scan_verdict", OP_CANNY_AUTO_THR: "canny_auto_thr",
-             OP_DIGEST: "digest", OP_REPEAT: "repeat"}
+             OP_DIGEST: "digest", OP_REPEAT: "repeat", OP_TILE_CUT: "tile_cut", OP_TILE_BLEND_U8: "tile_blend_u8"}
 
 EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", "i2i_igemm", "i2i_igemm_gn_parts", "i2i_igemm_route", "i2i_gn_stats",
            "i2i_gn_apply", "i2i_nop", "i2i_calib_mfma", "i2i_calib_stream", "i2i_layernorm", "i2i_softmax", "i2i_attention", "i2i_nchw_to_nhwc",
@@ -216,7 +232,8 @@ EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", 
            "i2i_merge_group_create", "i2i_merge_group_run", "i2i_merge_group_destroy", "i2i_run", "i2i_run_timed",
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
-           "i2i_plan_has_scale", "i2i_plan_set_scale", "i2i_digest", "i2i_plan_verify", "i2i_repeat"]
+           "i2i_plan_has_scale", "i2i_plan_set_scale", "i2i_digest", "i2i_plan_verify", "i2i_repeat",
+           "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_tile_positions"]
 
 
 class I2IError(RuntimeError):
@@ -269,7 +286,8 @@ class Library:
         L.i2i_sizeof_op.restype = C.c_size_t
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
                      "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
-                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr", "i2i_digest", "i2i_repeat"):
+                     "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr", "i2i_digest", "i2i_repeat",
+                     "i2i_tile_cut", "i2i_tile_blend_u8"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -280,6 +298,8 @@ class Library:
         L.i2i_resample_ksize.restype = C.c_int
         L.i2i_resample_tables.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
         L.i2i_resample_tables.restype = C.c_int
+        L.i2i_tile_positions.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int]
+        L.i2i_tile_positions.restype = C.c_int
         L.i2i_lanczos_ksize.argtypes = [C.c_int, C.c_int]
         L.i2i_lanczos_ksize.restype = C.c_int
         L.i2i_lanczos_tables.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int]
@@ -340,6 +360,15 @@ class Library:
         got = int(self.lib.i2i_resample_tables(int(code), int(in_size), int(out_size), bounds.ctypes.data, coeffs.ctypes.data, cap))
         self.check(min(got, 0))
         return got, bounds, coeffs
+
+    def tile_positions(self, length, tile, overlap):
+        """The library's own tile positions of one axis (i2i_tile_positions, host code) as a list of ints -- what a host that is not Python
+        computes; equal to image_ops.tile_positions.  Raises I2IError for arguments outside the layout rule."""
+        n = int(self.lib.i2i_tile_positions(int(length), int(tile), int(overlap), None, 0))
+        self.check(min(n, 0))
+        out = (C.c_int32 * n)()
+        self.check(min(int(self.lib.i2i_tile_positions(int(length), int(tile), int(overlap), C.addressof(out), n)), 0))
+        return list(out)
 
     def lanczos_tables(self, in_size, out_size, ksize_capacity=None):
         """The library's own tap tables (i2i_lanczos_tables, host code): (ksize, bounds int32 [out, 2], coeffs int32 [out, capacity]) as numpy

@@ -55,6 +55,8 @@ int dispatch(const i2i_op& op, void* stream) {
         case I2I_OP_CANNY_AUTO_THR: return i2i_canny_auto_thr(&op.u.canny_auto_thr, op.dtype, stream);
         case I2I_OP_DIGEST: return i2i_digest(&op.u.digest, op.dtype, stream);
         case I2I_OP_REPEAT: return i2i_repeat(&op.u.repeat, op.dtype, stream);
+        case I2I_OP_TILE_CUT: return i2i_tile_cut(&op.u.tile_cut, op.dtype, stream);
+        case I2I_OP_TILE_BLEND_U8: return i2i_tile_blend_u8(&op.u.tile_blend_u8, op.dtype, stream);
         default: return i2i::fail(I2I_ERR_BAD_ARG, "run: unknown opcode %d", op.opcode);
     }
 }

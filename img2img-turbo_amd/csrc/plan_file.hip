@@ -124,7 +124,12 @@ const std::vector<size_t>& ptr_fields(int opcode) {
         }
         return v;
     }();
+    static const std::vector<size_t> tile_cut = {PF(tile_cut, src), PF(tile_cut, dst), PF(tile_cut, reqs), PF(tile_cut, pos), PF(tile_cut, bad_mask)};
+    static const std::vector<size_t> tile_blend = {PF(tile_blend_u8, tiles), PF(tile_blend_u8, dst), PF(tile_blend_u8, reqs), PF(tile_blend_u8, pos),
+                                                   PF(tile_blend_u8, bad_mask)};
     switch (opcode) {
+        case I2I_OP_TILE_CUT: return tile_cut;
+        case I2I_OP_TILE_BLEND_U8: return tile_blend;
         case I2I_OP_REPEAT: return repeat;
         case I2I_OP_DIGEST: return digest;
         case I2I_OP_CANNY_AUTO_THR: return canny_auto;

@@ -822,3 +822,237 @@ extern "C" int i2i_canny_auto_thr(const i2i_canny_auto_thr_params* p, int dtype,
     hipLaunchKernelGGL(canny_select_kernel, dim3(gy), dim3(64), 0, s, *p);
     return i2i::check_launch("canny_auto_thr");
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Tiled forward at native resolution (i2i_tile_positions, i2i_tile_cut, i2i_tile_blend_u8; the contract is the comment of i2i_tile_request
+// in include/i2i_turbo.h): requests larger than the model size are cut into overlapping tiles, and the tile outputs are blended back with
+// an integer feather.  Both kernels follow resize_ragged_u8_kernel: grid y = request, grid x = a capacity hint, everything that differs
+// between requests is read from a device descriptor, and every workgroup judges its request before it touches a pixel.  Work is dealt
+// by ROWS: a wave owns one row of a tile (cut) or of the image (blend) at a time, so everything that depends on the row -- tile slot,
+// plane, source row, the covering ky set and its weights -- is wave-uniform, and the lanes run along the row (coalesced).
+namespace {
+
+constexpr int TILE_MAX_X = 1024;                             // workgroups per request at most
+constexpr int TILE_WAVES = 4;                                // waves of a workgroup of 256
+
+// 0 = empty slot, 1 = run, -1 = rejected; as ragged_verdict (all 256 threads, i2i_smem holds one int).  `px`: bytes per pixel times planes
+// is the request's size; `ordered`: the blend's extra condition on the positions of an axis.
+__device__ int tile_verdict(const i2i_tile_request& d, const int32_t* __restrict__ pos, int64_t pos_len, int64_t arena_bytes, int planes, int px,
+                            int tw, int th, int tiles_capacity, bool ordered) {
+    if (d.h == 0 || d.w == 0) return 0;
+    bool ok = d.h > 0 && d.w > 0 && d.nx >= 1 && d.ny >= 1 && d.off >= 0 && (d.off & 3) == 0 && d.off <= arena_bytes && d.xs_off >= 0 && d.ys_off >= 0 &&
+              d.xs_off <= pos_len && d.ys_off <= pos_len && d.tile0 >= 0 && d.tile0 <= tiles_capacity && tw <= d.w && th <= d.h;
+    if (ok) {                                                // sizes as quotients: no product can overflow
+        const int64_t pxs = (int64_t)d.h * d.w;              // < 2^62
+        ok = pxs <= (arena_bytes - d.off) / px / planes && d.nx <= pos_len - d.xs_off && d.ny <= pos_len - d.ys_off &&
+             d.nx <= (tiles_capacity - d.tile0) / d.ny;
+    }
+    int* verdict = (int*)i2i_smem;
+    if (threadIdx.x == 0) *verdict = ok ? 1 : 0;
+    __syncthreads();
+    if (ok) {
+        bool pos_ok = true;
+        for (int axis = 0; axis < 2; ++axis) {
+            const int32_t* __restrict__ q = pos + (axis ? d.ys_off : d.xs_off);
+            const int cnt = axis ? d.ny : d.nx, ext = axis ? d.h : d.w, t = axis ? th : tw;
+            for (int k = (int)threadIdx.x; k < cnt; k += 256) {
+                const int x = q[k];
+                pos_ok = pos_ok && x >= 0 && x <= ext - t;
+                if (ordered) {
+                    if (k + 1 < cnt) pos_ok = pos_ok && q[k + 1] > x;
+                    if (k + 3 < cnt) pos_ok = pos_ok && q[k + 3] >= x && q[k + 3] - x >= t;
+                }
+            }
+        }
+        if (!pos_ok) *verdict = 0;                           // (every writer stores the same 0)
+    }
+    __syncthreads();
+    const int v = *verdict;
+    __syncthreads();                                         // the word is reused for the workgroup's next request
+    return v ? 1 : -1;
+}
+
+// VEC = 4: tile rows of whole dwords (tw * px_bytes % 4 == 0; every tile row of dst then starts on a dword); VEC = 1: bytes
+template <int VEC>
+__device__ __forceinline__ void tile_cut_request(const i2i_tile_cut_params& p, const i2i_tile_request& d) {
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int px = p.px_bytes;
+    const int64_t rowb = (int64_t)p.tw * px;                 // bytes of a tile row
+    const int units = (int)(rowb / VEC);
+    const int64_t rows = (int64_t)d.nx * d.ny * p.planes * p.th;
+    const int32_t* __restrict__ xs = p.pos + d.xs_off;
+    const int32_t* __restrict__ ys = p.pos + d.ys_off;
+    const uint8_t* __restrict__ base = (const uint8_t*)p.src;                 // the ARENA: `a` below is an arena offset
+    uint8_t* __restrict__ dst = (uint8_t*)p.dst;
+    for (int64_t row = (int64_t)blockIdx.x * TILE_WAVES + wave; row < rows; row += (int64_t)gridDim.x * TILE_WAVES) {
+        const int r = (int)(row % p.th);
+        const int64_t tp = row / p.th;
+        const int pl = (int)(tp % p.planes), t = (int)(tp / p.planes);
+        const int ky = t / d.nx, kx = t - ky * d.nx;
+        const int64_t a0 = d.off + (((int64_t)pl * d.h + ys[ky] + r) * d.w + xs[kx]) * px;
+        uint8_t* __restrict__ o = dst + ((((int64_t)(d.tile0 + t) * p.planes + pl) * p.th + r) * rowb);
+        for (int u = lane; u < units; u += 64) {
+            if constexpr (VEC == 4) {
+                const int64_t a = a0 + 4 * (int64_t)u;
+                const int sh = 8 * (int)(a & 3);
+                uint32_t v;
+                if (sh == 0) {
+                    v = *(const uint32_t*)(base + a);
+                } else if ((a & ~(int64_t)3) + 8 <= p.arena_bytes) {
+                    const uint32_t* q = (const uint32_t*)(base + (a & ~(int64_t)3));
+                    v = (q[0] >> sh) | (q[1] << (32 - sh));
+                } else {                                     // the arena's last dword: the request's own bytes only
+                    v = (uint32_t)base[a] | ((uint32_t)base[a + 1] << 8) | ((uint32_t)base[a + 2] << 16) | ((uint32_t)base[a + 3] << 24);
+                }
+                *(uint32_t*)(o + 4 * (int64_t)u) = v;
+            } else {
+                o[u] = base[a0 + u];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void tile_cut_kernel(const i2i_tile_cut_params p) {
+    for (int b = (int)blockIdx.y; b < p.n; b += (int)gridDim.y) {
+        const i2i_tile_request d = p.reqs[b];
+        const int v = tile_verdict(d, p.pos, p.pos_len, p.arena_bytes, p.planes, p.px_bytes, p.tw, p.th, p.tiles_capacity, false);
+        if (v < 0 && p.bad_mask && blockIdx.x == 0 && threadIdx.x == 0) agent_or_u32(p.bad_mask, 1u << (b & 31));
+        if (v <= 0) continue;
+        if (((int64_t)p.tw * p.px_bytes) % 4 == 0) tile_cut_request<4>(p, d);
+        else tile_cut_request<1>(p, d);
+    }
+}
+
+__device__ __forceinline__ int feather(int i, int t, int ramp) {
+    const int a = i + 1, b = t - i;
+    const int m = a < b ? a : b;
+    return m < ramp ? m : ramp;
+}
+
+// VEC = 4: image rows of whole dwords (w * c % 4 == 0; the request's base is 4-byte aligned); VEC = 1: bytes.  Returns whether this thread
+// met a byte that no tile covers.
+template <int VEC>
+__device__ __forceinline__ bool tile_blend_request(const i2i_tile_blend_u8_params& p, const i2i_tile_request& d) {
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int c = p.c;
+    const int64_t rowb = (int64_t)d.w * c;
+    const int units = (int)(rowb / VEC);
+    const int64_t trow = (int64_t)p.tw * c;                  // bytes of a tile row
+    const int32_t* __restrict__ xs = p.pos + d.xs_off;
+    const int32_t* __restrict__ ys = p.pos + d.ys_off;
+    const uint8_t* __restrict__ tiles = (const uint8_t*)p.tiles;
+    uint8_t* __restrict__ dst = (uint8_t*)p.dst + d.off;
+    bool hole = false;
+    for (int y = (int)blockIdx.x * TILE_WAVES + wave; y < d.h; y += (int)gridDim.x * TILE_WAVES) {
+        // the tile rows over y (wave-uniform; at most 3, the positions increase): first tile of the tile row, row inside the tile, weight
+        int nky = 0, wy[3];
+        int64_t rbase[3];
+        for (int ky = 0; ky < d.ny && nky < 3; ++ky) {
+            const int y0 = ys[ky];
+            if (y0 > y) break;
+            if (y - y0 < p.th) {
+                wy[nky] = feather(y - y0, p.th, p.ramp);
+                rbase[nky] = (((int64_t)d.tile0 + (int64_t)ky * d.nx) * p.th + (y - y0)) * trow;
+                ++nky;
+            }
+        }
+        uint8_t* __restrict__ o = dst + (int64_t)y * rowb;
+        for (int u = lane; u < units; u += 64) {
+            uint32_t word = 0;
+#pragma unroll
+            for (int b = 0; b < VEC; ++b) {
+                const int j = u * VEC + b, x = j / c, ch = j - x * c;
+                uint32_t num = 0, den = 0;
+                for (int kx = 0; kx < d.nx; ++kx) {
+                    const int x0 = xs[kx];
+                    if (x0 > x) break;
+                    if (x - x0 >= p.tw) continue;
+                    const uint32_t wx = (uint32_t)feather(x - x0, p.tw, p.ramp);
+                    const int64_t within = (int64_t)kx * p.th * trow + (int64_t)(x - x0) * c + ch;
+                    for (int k = 0; k < nky; ++k) {
+                        const uint32_t w = wx * (uint32_t)wy[k];
+                        num += w * tiles[rbase[k] + within];
+                        den += w;
+                    }
+                }
+                uint32_t out = 0;
+                if (den) out = (2 * num + den) / (2 * den);
+                else hole = true;
+                word |= out << (8 * b);
+            }
+            if constexpr (VEC == 4) *(uint32_t*)(o + 4 * (int64_t)u) = word;
+            else o[u] = (uint8_t)word;
+        }
+    }
+    return hole;
+}
+
+__global__ __launch_bounds__(256) void tile_blend_u8_kernel(const i2i_tile_blend_u8_params p) {
+    for (int b = (int)blockIdx.y; b < p.n; b += (int)gridDim.y) {
+        const i2i_tile_request d = p.reqs[b];
+        const int v = tile_verdict(d, p.pos, p.pos_len, p.arena_bytes, 1, p.c, p.tw, p.th, p.tiles_capacity, true);
+        if (v < 0 && p.bad_mask && blockIdx.x == 0 && threadIdx.x == 0) agent_or_u32(p.bad_mask, 1u << (b & 31));
+        if (v <= 0) continue;
+        const bool hole = (((int64_t)d.w * p.c) % 4 == 0) ? tile_blend_request<4>(p, d) : tile_blend_request<1>(p, d);
+        if (hole && p.bad_mask) agent_or_u32(p.bad_mask, 1u << (b & 31));
+    }
+}
+
+// what both entries check alike; `what` names the entry
+int tile_args(const char* what, int n, int planes, int px, int tw, int th, int tiles_capacity, int64_t grid_units, int64_t arena_bytes, int64_t pos_len,
+              const void* arena, const void* tiles, const void* reqs, const void* pos, const void* bad_mask) {
+    if (n < 0) return i2i::fail(I2I_ERR_BAD_ARG, "%s: n = %d < 0", what, n);
+    if (planes < 1) return i2i::fail(I2I_ERR_BAD_ARG, "%s: planes = %d < 1", what, planes);
+    if (px < 1 || px > 4) return i2i::fail(I2I_ERR_BAD_ARG, "%s: %d bytes per pixel outside 1..4", what, px);
+    if (tw < 1 || th < 1) return i2i::fail(I2I_ERR_BAD_ARG, "%s: tile extent (tw = %d, th = %d) must be positive", what, tw, th);
+    if (tiles_capacity < 0) return i2i::fail(I2I_ERR_BAD_ARG, "%s: tiles_capacity = %d < 0", what, tiles_capacity);
+    if (grid_units < 1) return i2i::fail(I2I_ERR_BAD_ARG, "%s: grid_units must be >= 1", what);
+    if (arena_bytes < 0 || pos_len < 0) return i2i::fail(I2I_ERR_BAD_ARG, "%s: negative arena_bytes / pos_len", what);
+    if (n == 0) return I2I_OK;
+    if (!arena || !tiles || !reqs || !pos) return i2i::fail(I2I_ERR_BAD_ARG, "%s: null pointer (arena, tiles, reqs, pos)", what);
+    if (((uintptr_t)arena | (uintptr_t)tiles | (uintptr_t)pos | (uintptr_t)bad_mask) & 3)
+        return i2i::fail(I2I_ERR_BAD_ARG, "%s: the arena, the tile batch, pos and bad_mask must be 4-byte aligned", what);
+    if ((uintptr_t)reqs & 7) return i2i::fail(I2I_ERR_BAD_ARG, "%s: reqs must be 8-byte aligned", what);
+    return I2I_OK;
+}
+
+dim3 tile_grid(int n, int64_t grid_units) {
+    const int64_t bx = (grid_units + 1023) / 1024;
+    return dim3((unsigned)(bx < TILE_MAX_X ? bx : TILE_MAX_X), (unsigned)(n < 65535 ? n : 65535));
+}
+
+}  // namespace
+
+extern "C" int i2i_tile_positions(int L, int t, int ov, int32_t* out, int capacity) {
+    if (t < 8 || t % 8 != 0) return i2i::fail(I2I_ERR_BAD_ARG, "tile_positions: tile extent %d is not a positive multiple of 8", t);
+    if (ov < 0 || ov % 8 != 0 || ov > t / 2) return i2i::fail(I2I_ERR_BAD_ARG, "tile_positions: overlap %d (a multiple of 8 in 0 .. %d)", ov, t / 2);
+    if (L < t) return i2i::fail(I2I_ERR_BAD_ARG, "tile_positions: length %d is smaller than the tile extent %d", L, t);
+    const int s = t - ov;
+    const int64_t n = 1 + ((int64_t)L - t + s - 1) / s;
+    if (n > 0x7fffffff) return i2i::fail(I2I_ERR_BAD_ARG, "tile_positions: more than 2^31 - 1 tiles");
+    if (!out) return (int)n;
+    if (capacity < n) return i2i::fail(I2I_ERR_BAD_ARG, "tile_positions: capacity %d < %d tiles", capacity, (int)n);
+    for (int64_t k = 0; k < n; ++k) out[k] = (int32_t)(k * s < (int64_t)L - t ? k * s : (int64_t)L - t);
+    return (int)n;
+}
+
+extern "C" int i2i_tile_cut(const i2i_tile_cut_params* p, int dtype, void* stream) {
+    (void)dtype;
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "tile_cut: null pointer");
+    const int rc = tile_args("tile_cut", p->n, p->planes, p->px_bytes, p->tw, p->th, p->tiles_capacity, p->grid_units, p->arena_bytes, p->pos_len,
+                             p->src, p->dst, p->reqs, p->pos, p->bad_mask);
+    if (rc != I2I_OK || p->n == 0) return rc;
+    hipLaunchKernelGGL(tile_cut_kernel, tile_grid(p->n, p->grid_units), dim3(256), 16, (hipStream_t)stream, *p);
+    return i2i::check_launch("tile_cut");
+}
+
+extern "C" int i2i_tile_blend_u8(const i2i_tile_blend_u8_params* p, int dtype, void* stream) {
+    (void)dtype;
+    if (!p) return i2i::fail(I2I_ERR_BAD_ARG, "tile_blend_u8: null pointer");
+    if (p->ramp < 1 || p->ramp > 256) return i2i::fail(I2I_ERR_BAD_ARG, "tile_blend_u8: ramp = %d outside 1..256", p->ramp);
+    const int rc = tile_args("tile_blend_u8", p->n, 1, p->c, p->tw, p->th, p->tiles_capacity, p->grid_units, p->arena_bytes, p->pos_len,
+                             p->dst, p->tiles, p->reqs, p->pos, p->bad_mask);
+    if (rc != I2I_OK || p->n == 0) return rc;
+    hipLaunchKernelGGL(tile_blend_u8_kernel, tile_grid(p->n, p->grid_units), dim3(256), 16, (hipStream_t)stream, *p);
+    return i2i::check_launch("tile_blend_u8");
+}

@@ -9,7 +9,7 @@ from typing import Optional
 
 import torch
 
-from .pix2pix_turbo import TurboGeneratorBase, _NetHandle, seed_argument
+from .pix2pix_turbo import TurboGeneratorBase, _NetHandle, _bind, seed_argument
 from .weights import GeneratorWeights, from_cyclegan_checkpoint, load_checkpoint_file, load_sd_turbo_base
 
 PRETRAINED = {  # src/cyclegan_turbo.py:126-149: name -> (checkpoint file, caption, direction)
@@ -46,7 +46,7 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         self.vae_enc._model = self.vae_dec._model = self.unet._model = self
 
     @torch.no_grad()
-    def forward_u8(self, images_u8, *args, resize=None, resize_back=False, image_prep=None, **kw):
+    def forward_u8(self, images_u8, *args, resize=None, resize_back=False, image_prep=None, tile=None, tile_overlap=64, tile_batch=8, **kw):
         """uint8 HWC in/out on the device: ``Normalize([0.5],[0.5])(to_tensor(img))`` (src/inference_unpaired.py:47) and
         ``ToPILImage()(out*0.5+0.5)`` (:53) run inside the boundary kernels.  ``resize=(width, height)`` applies the script's
         ``transforms.Resize(..., LANCZOS)`` (:40-47, e.g. (512, 512) for "resize_512x512") before the generator and
@@ -56,7 +56,14 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         file each -- with ``resize=(width, height)`` or ``image_prep="resize_512x512"`` / ``"resize_256x256"`` (and their short forms): two
         launches bring the batch to the model size and, with ``resize_back=True``, two more take every output back to its request's own size
         (image_ops.lanczos_resize_u8_ragged); the result is then a list, element b bit-identical to the per-image resize.  A list without a
-        common size in front of the generator (no ``resize``, ``image_prep="resized_crop_512"`` / ``"no_resize"``) is a ValueError."""
+        common size in front of the generator (no ``resize``, ``image_prep="resized_crop_512"`` / ``"no_resize"``) is a ValueError.
+        ``tile=(tile width, tile height)`` with ``tile_overlap`` / ``tile_batch``: the request keeps its size and runs as overlapping tiles
+        of the model size, cut and feather-blended on the device, as Pix2Pix_Turbo.forward_u8 describes (noise rule, refusals and the
+        caveat on picture quality included); ``resize=`` / ``image_prep=`` apply first, ``resize_back=True`` is refused, and a list of
+        requests of different sizes needs no common size."""
+        if tile is not None:
+            return self._forward_u8_tiled(images_u8, _bind(("direction", "caption", "caption_emb"), args, kw), resize=resize, resize_back=resize_back,
+                                          image_prep=image_prep, tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch)
         if isinstance(images_u8, (list, tuple)):
             return self._forward_u8_list(list(images_u8), *args, resize=resize, resize_back=resize_back, image_prep=image_prep, **kw)
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[-1] == 3
@@ -75,6 +82,43 @@ class CycleGAN_Turbo(TurboGeneratorBase):
             with self._on_device():
                 out = lanczos_resize_u8(out, (in_hw[1], in_hw[0]), self.lib)
         return out
+
+    def _forward_u8_tiled(self, images, opts, *, resize, resize_back, image_prep, tile, tile_overlap, tile_batch):
+        """forward_u8 with ``tile=`` (see there)."""
+        from . import image_ops
+        unknown = set(opts) - {"direction", "caption", "caption_emb", "eps", "seed"}
+        if unknown:
+            raise TypeError("forward_u8: unexpected arguments %s" % sorted(unknown))
+        self._tile_refusals(tile, tile_batch, eps=opts.get("eps"), resize_back=resize_back)
+        stacked = torch.is_tensor(images)
+        sizes = {"resize_256": (256, 256), "resize_256x256": (256, 256), "resize_512": (512, 512), "resize_512x512": (512, 512)}
+        with self._on_device():
+            if stacked:
+                if image_prep is not None:
+                    images = image_ops.apply_image_prep(images, image_prep, self.lib)
+                if resize is not None:
+                    images = image_ops.lanczos_resize_u8(images, resize, self.lib)
+            elif image_prep is not None and image_prep != "no_resize" and image_prep not in sizes:
+                raise ValueError("image_prep %r does not apply to a list of images of different sizes" % (image_prep,))
+            elif resize is not None or image_prep in sizes:
+                size = (int(resize[0]), int(resize[1])) if resize is not None else sizes[image_prep]
+                images, stacked = image_ops.lanczos_resize_u8_ragged(list(images), size, self.lib), True
+        items = list(images.unbind(0)) if stacked else list(images)
+        if not items or any(not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3 for t in items):
+            raise ValueError("forward_u8(tile=...): uint8 [B, H, W, 3], or a list of uint8 [H, W, 3] requests")
+        direction = opts.get("direction") or self.direction
+        assert direction in ("a2b", "b2a")
+        caption_enc = opts.get("caption_emb")
+        if caption_enc is None:
+            caption = opts.get("caption") or self.caption
+            assert caption is not None
+            caption_enc = self.encode_prompt(caption)
+
+        def chunk(tiles, cap, eps, noise):
+            return self.forward(tiles, direction=direction, caption_emb=cap, eps=eps, _u8_io=(2.0, -1.0))
+
+        return self._forward_tiles(items, stacked, chunk, tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch, seed=opts.get("seed"),
+                                   stochastic=False, caption_enc=caption_enc)[0]
 
     def _forward_u8_list(self, images, *args, resize, resize_back, image_prep, **kw):
         """forward_u8 for a list of images of different sizes (see there)."""

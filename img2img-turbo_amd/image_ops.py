@@ -277,6 +277,195 @@ def lanczos_resize_u8_ragged(images, size, lib=None, *, resample="lanczos"):
     return dst[:n * oh * ow * c].view(n, oh, ow, c) if (oh * ow * c) % 4 == 0 else torch.stack(views)
 
 
+# ---- tiled forward at native resolution: i2i_tile_cut / i2i_tile_blend_u8 (include/i2i_turbo.h, the note above i2i_tile_request) ----
+# one request as the kernels read it from device memory (i2i_tile_request, 48 bytes)
+TILE_REQUEST_DTYPE = np.dtype([("off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("tile0", "<i4"), ("nx", "<i4"), ("ny", "<i4"), ("xs_off", "<i4"),
+                               ("ys_off", "<i4"), ("reserved", "<i4", (3,))])
+assert TILE_REQUEST_DTYPE.itemsize == 48
+
+
+def tile_positions(length, tile, overlap):
+    """THE layout rule of one axis (stated at i2i_tile_request; i2i_tile_positions is its C twin): stride s = tile - overlap, n = 1 +
+    ceil((length - tile) / s) tiles at min(k * s, length - tile).  ValueError outside tile % 8 == 0, overlap % 8 == 0, 0 <= overlap <=
+    tile / 2, length >= tile."""
+    L, t, ov = int(length), int(tile), int(overlap)
+    if t < 8 or t % 8:
+        raise ValueError("tile extent %d is not a positive multiple of 8" % t)
+    if ov < 0 or ov % 8 or ov > t // 2:
+        raise ValueError("tile overlap %d (a multiple of 8 in 0 .. %d, half the tile extent %d)" % (ov, t // 2, t))
+    if L < t:
+        raise ValueError("a request of length %d is smaller than the tile extent %d" % (L, t))
+    s = t - ov
+    return [min(k * s, L - t) for k in range(1 + -(-(L - t) // s))]
+
+
+TileTable = collections.namedtuple("TileTable", "desc pos offs arena_bytes planes px_bytes tw th units_cut units_blend desc_dev pos_dev")
+
+
+class TileLayout:
+    """The tiles of a batch of requests (host-side geometry, no device work): ``sizes[b]`` = (h, w), ``tile`` = (tw, th), ``overlap``.
+    ``xs[b]`` / ``ys[b]``: the positions of request b, ``counts[b]`` = (nx, ny), ``tile0[b]`` its first tile slot, ``T`` the number of
+    tiles, ``origins[t]`` = (request, y0, x0) of tile t (row-major per request, request after request).  ``table()`` packs the device
+    descriptors for one tensor kind."""
+
+    def __init__(self, sizes, tile, overlap):
+        self.sizes = [(int(h), int(w)) for h, w in sizes]
+        self.tile = (int(tile[0]), int(tile[1]))
+        self.overlap = int(overlap)
+        tw, th = self.tile
+        self.xs = [tile_positions(w, tw, self.overlap) for _, w in self.sizes]
+        self.ys = [tile_positions(h, th, self.overlap) for h, _ in self.sizes]
+        self.counts = [(len(x), len(y)) for x, y in zip(self.xs, self.ys)]
+        self.tile0, self.origins = [], []
+        for b, (x, y) in enumerate(zip(self.xs, self.ys)):
+            self.tile0.append(len(self.origins))
+            self.origins += [(b, y0, x0) for y0 in y for x0 in x]
+        self.T = len(self.origins)
+        self.request_of_tile = [o[0] for o in self.origins]
+        self._tables = {}
+
+    def table(self, planes, px_bytes, div=1, device=None):
+        """The descriptors of the requests as [planes][h][w] pixels of ``px_bytes`` bytes packed densely, request after request at 4-byte
+        aligned offsets: TileTable(desc TILE_REQUEST_DTYPE [n], pos int32 pool, offs, arena_bytes, .., tw, th, grid hints, and -- with
+        ``device`` -- both as device tensors, cached).  ``div=8``: the latent-resolution twin (the noise rule): extents ceil(. / 8),
+        positions // 8, tile extent // 8."""
+        key = (int(planes), int(px_bytes), int(div), str(device))
+        if key not in self._tables:
+            planes, px_bytes, div = key[:3]
+            n = len(self.sizes)
+            tw, th = self.tile[0] // div, self.tile[1] // div
+            desc = np.zeros(n, dtype=TILE_REQUEST_DTYPE)
+            pool, offs, off, units_cut, units_blend = [], [], 0, 1, 1
+            for b, (h, w) in enumerate(self.sizes):
+                h, w = -(-h // div), -(-w // div)
+                nx, ny = self.counts[b]
+                xs_off = sum(len(p) for p in pool)
+                pool += [[x // div for x in self.xs[b]], [y // div for y in self.ys[b]]]
+                desc[b] = (off, h, w, self.tile0[b], nx, ny, xs_off, xs_off + nx, (0, 0, 0))
+                offs.append(off)
+                off += _align4(planes * h * w * px_bytes)
+                units_cut = max(units_cut, nx * ny * planes * th * -(-tw * px_bytes // 4))
+                units_blend = max(units_blend, h * w * px_bytes)
+            pos = np.array([v for p in pool for v in p] or [0], dtype=np.int32)
+            dd = pd = None
+            if device is not None:
+                dd = torch.from_numpy(desc.view(np.int64).reshape(-1).copy() if n else np.zeros(6, dtype=np.int64)).to(device)
+                pd = torch.from_numpy(pos.copy()).to(device)
+            self._tables[key] = TileTable(desc, pos, offs, off, planes, px_bytes, tw, th, units_cut, units_blend, dd, pd)
+        return self._tables[key]
+
+
+_TILE_LAYOUTS = collections.OrderedDict()    # (sizes, tile, overlap) -> TileLayout with its device tables; small LRU like _RAGGED_POOLS
+_TILE_LAYOUTS_MAX = 16
+
+
+def tile_layout(sizes, tile, overlap):
+    """The cached TileLayout of a set of request sizes [(h, w)], ``tile`` = (tw, th) and ``overlap``: positions, tile counts and (through
+    ``.table(planes, px_bytes, div, device)``) the descriptors as device tensors, cached like the tap tables.  ValueError if the layout
+    rule refuses an argument (tile_positions)."""
+    key = (tuple((int(h), int(w)) for h, w in sizes), (int(tile[0]), int(tile[1])), int(overlap))
+    if key in _TILE_LAYOUTS:
+        _TILE_LAYOUTS.move_to_end(key)
+    else:
+        _TILE_LAYOUTS[key] = TileLayout(*key)
+        while len(_TILE_LAYOUTS) > _TILE_LAYOUTS_MAX:
+            _TILE_LAYOUTS.popitem(last=False)
+    return _TILE_LAYOUTS[key]
+
+
+def _pack_arena(items):
+    """The flattened tensors as ONE uint8 arena, each padded to a multiple of 4 bytes (what TileLayout.table's offsets assume)."""
+    dev = items[0].device
+    pad = torch.zeros(3, dtype=torch.uint8, device=dev)
+    parts = []
+    for t in items:
+        flat = t.contiguous().view(torch.uint8).reshape(-1)
+        parts.append(flat)
+        if flat.numel() % 4:
+            parts.append(pad[:4 - flat.numel() % 4])
+    return torch.cat(parts) if len(parts) > 1 else parts[0]
+
+
+def _tile_cut(items, layout, table, out, lib):
+    dev = items[0].device
+    assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
+    from . import ops as O
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        src = _pack_arena(items)
+        if src.data_ptr() % 4:                               # (a single request that is a view starting off a dword)
+            src = src.clone()
+        assert src.numel() == table.arena_bytes
+        _, p = O.tile_cut(src, out, table.desc_dev, table.pos_dev, n=len(items), planes=table.planes, px_bytes=table.px_bytes, tw=table.tw, th=table.th,
+                          tiles_capacity=layout.T, grid_units=table.units_cut)
+        lib.check(lib.lib.i2i_tile_cut(C.addressof(p), 0, stream))
+    return out
+
+
+def _request_list(images, what):
+    if torch.is_tensor(images):
+        assert images.dim() == 4, "%s: a stacked batch is [B, ...] with three more dimensions" % what
+        return list(images.unbind(0))
+    items = list(images)
+    if not items:
+        raise ValueError("%s: no requests" % what)
+    return items
+
+
+def tile_cut_u8(images, tile, overlap, lib=None):
+    """Every tile of every request in ONE launch (i2i_tile_cut): ``images`` a uint8 [B, H, W, C] tensor or a list of uint8 [H_b, W_b, C]
+    tensors of different sizes on one device (same C <= 4) -> (tiles uint8 [T, th, tw, C], the TileLayout).  ``tile`` = (tw, th); bit-equal to
+    slicing.  Asynchronous on the current stream."""
+    lib = lib or _capi.default_library()
+    items = _request_list(images, "tile_cut_u8")
+    c, dev = int(items[0].shape[-1]), items[0].device
+    if not (1 <= c <= 4) or any(t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != c or t.device != dev for t in items):
+        raise ValueError("tile_cut_u8: uint8 [H, W, C] requests that share the channel count (1..4) and the device")
+    layout = tile_layout([t.shape[:2] for t in items], tile, overlap)
+    out = torch.empty((layout.T, layout.tile[1], layout.tile[0], c), dtype=torch.uint8, device=dev)
+    return _tile_cut(items, layout, layout.table(1, c, 1, dev), out, lib), layout
+
+
+def tile_cut_planes(fields, layout, lib=None, div=8):
+    """The noise rule: ``fields`` a list of fp32 [P, ceil(H_b / div), ceil(W_b / div)] tensors (or one stacked [B, P, ., .]), one per request
+    of ``layout`` -> fp32 [T, P, th / div, tw / div], tile t the crop of its request's field at (y0 // div, x0 // div).  One launch."""
+    lib = lib or _capi.default_library()
+    items = _request_list(fields, "tile_cut_planes")
+    planes, dev = int(items[0].shape[0]), items[0].device
+    want = [(planes, -(-h // div), -(-w // div)) for h, w in layout.sizes]
+    if len(items) != len(want) or any(t.dtype != torch.float32 or tuple(t.shape) != s or t.device != dev for t, s in zip(items, want)):
+        raise ValueError("tile_cut_planes: fp32 fields of shapes %s expected, got %s" % (want, [tuple(t.shape) for t in items]))
+    if layout.tile[0] % div or layout.tile[1] % div:
+        raise ValueError("tile_cut_planes: the tile %s is not a multiple of %d" % (layout.tile, div))
+    out = torch.empty((layout.T, planes, layout.tile[1] // div, layout.tile[0] // div), dtype=torch.float32, device=dev)
+    return _tile_cut(items, layout, layout.table(planes, 4, div, dev), out, lib)
+
+
+def tile_blend_u8(tiles, layout, lib=None, *, ramp=None, stack=False):
+    """The inverse of tile_cut_u8 (i2i_tile_blend_u8, one launch): ``tiles`` uint8 [T, th, tw, C] tile outputs -> a list of uint8
+    [H_b, W_b, C] images (views of one arena), or with ``stack=True`` one [B, H, W, C] tensor.  Overlaps are blended with the integer
+    feather of i2i_tile_blend_u8_params; ``ramp`` defaults to max(overlap, 1).  Asynchronous on the current stream."""
+    lib = lib or _capi.default_library()
+    tw, th = layout.tile
+    assert tiles.dtype == torch.uint8 and tiles.dim() == 4 and tuple(tiles.shape[:3]) == (layout.T, th, tw) and 1 <= tiles.shape[-1] <= 4
+    c, dev = int(tiles.shape[-1]), tiles.device
+    assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
+    from . import ops as O
+    table = layout.table(1, c, 1, dev)
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        dst = torch.empty(max(table.arena_bytes, 4), dtype=torch.uint8, device=dev)
+        _, p = O.tile_blend_u8(tiles.contiguous(), dst, table.desc_dev, table.pos_dev, n=len(layout.sizes), c=c,
+                               ramp=max(layout.overlap, 1) if ramp is None else int(ramp), tw=tw, th=th, tiles_capacity=layout.T,
+                               grid_units=table.units_blend)
+        lib.check(lib.lib.i2i_tile_blend_u8(C.addressof(p), 0, stream))
+    views = [dst[o:o + h * w * c].view(h, w, c) for o, (h, w) in zip(table.offs, layout.sizes)]
+    if not stack:
+        return views
+    h, w = layout.sizes[0]
+    return dst[:len(views) * h * w * c].view(len(views), h, w, c) if (h * w * c) % 4 == 0 and len(set(layout.sizes)) == 1 else torch.stack(views)
+
+
 def canny_thresholds(low, high):
     """The two ints the kernels compare against: float thresholds floored (the magnitudes are integers, so ``mag > floor(t)`` is
     ``mag > t``); the kernels swap them if low > high."""

@@ -209,6 +209,31 @@ def resize_u8_ragged(src, dst, images, tables, *, n, c, axis, grid_units, bad_ma
     return K.OP_RESIZE_U8_RAGGED, _keep(p, src, dst, images, tables, bad_mask)
 
 
+def tile_cut(src, dst, reqs, pos, *, n, planes, px_bytes, tw, th, tiles_capacity, grid_units, bad_mask=None, arena_bytes=None, pos_len=None):
+    """Every tile of every request of a ragged batch in one launch (i2i_tile_cut_params): ``src`` the request arena, ``dst`` the tile batch
+    [tiles_capacity][planes][th][tw] pixels of ``px_bytes`` bytes, ``reqs`` a device tensor of n 48-byte i2i_tile_request descriptors,
+    ``pos`` the int32 pool of positions.  All are read at run time; ``grid_units`` sizes the grid only."""
+    p = K.TileCutParams()
+    p.src, p.dst, p.reqs, p.pos, p.bad_mask = ptr(src), ptr(dst), ptr(reqs), ptr(pos), ptr(bad_mask)
+    p.arena_bytes = src.numel() * src.element_size() if arena_bytes is None else int(arena_bytes)
+    p.pos_len = pos.numel() if pos_len is None else int(pos_len)
+    p.n, p.planes, p.px_bytes, p.tw, p.th = int(n), int(planes), int(px_bytes), int(tw), int(th)
+    p.tiles_capacity, p.grid_units = int(tiles_capacity), int(grid_units)
+    return K.OP_TILE_CUT, _keep(p, src, dst, reqs, pos, bad_mask)
+
+
+def tile_blend_u8(tiles, dst, reqs, pos, *, n, c, ramp, tw, th, tiles_capacity, grid_units, bad_mask=None, arena_bytes=None, pos_len=None):
+    """The inverse of tile_cut for uint8 tile outputs [tiles_capacity][th][tw][c] with the integer feather of i2i_tile_blend_u8_params;
+    ``dst`` is the request arena the descriptors' offsets refer to."""
+    p = K.TileBlendU8Params()
+    p.tiles, p.dst, p.reqs, p.pos, p.bad_mask = ptr(tiles), ptr(dst), ptr(reqs), ptr(pos), ptr(bad_mask)
+    p.arena_bytes = dst.numel() * dst.element_size() if arena_bytes is None else int(arena_bytes)
+    p.pos_len = pos.numel() if pos_len is None else int(pos_len)
+    p.n, p.c, p.ramp, p.tw, p.th = int(n), int(c), int(ramp), int(tw), int(th)
+    p.tiles_capacity, p.grid_units = int(tiles_capacity), int(grid_units)
+    return K.OP_TILE_BLEND_U8, _keep(p, tiles, dst, reqs, pos, bad_mask)
+
+
 def twin_fold(dst, bias, pre, cur, rg, *, bias_pre=None, bias_cur=None):
     """dst[N][K] (+ bias[N]) = the TwinConv fold of two packed layers at the device scale rg[0] (i2i_twin_fold_params).  ``pre`` / ``cur``:
     (w0 fp32 [N][K], A fp32 [rank][K] or None, B fp32 [N][rank] or None)."""

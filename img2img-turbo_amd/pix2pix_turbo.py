@@ -336,6 +336,68 @@ class TurboGeneratorBase(torch.nn.Module):
             self._last_plan = plan
             return plan.out.clone()
 
+    # ---- tiled forward at native resolution (include/i2i_turbo.h, the note above i2i_tile_request; DESIGN.md "Tiled forward") ----
+    def _tile_refusals(self, tile, tile_batch, *, eps=None, noise_map=None, variations=1, resize_back=False):
+        """The argument combinations a tiled forward_u8 refuses (ValueError with the reason)."""
+        if not (isinstance(tile, (tuple, list)) and len(tile) == 2 and all(isinstance(v, numbers.Integral) for v in tile)):
+            raise ValueError("tile=%r (a pair (tile width, tile height) of multiples of 8)" % (tile,))
+        if int(tile_batch) < 1:
+            raise ValueError("tile_batch=%r (an integer >= 1)" % (tile_batch,))
+        if eps is not None or noise_map is not None:
+            raise ValueError("tile= draws one noise field per request and crops it per tile (seed= or torch.randn): do not pass eps= / noise_map= with it")
+        if int(variations) > 1:
+            raise ValueError("tile= together with variations=%d is not supported" % int(variations))
+        if resize_back:
+            raise ValueError("tile= keeps the request's size: resize_back=True has nothing to undo")
+        if self.health_per_image:
+            raise ValueError("tile= on a model with health_per_image=True: the images of a tile batch are tiles, not requests")
+        if self.fingerprint_mode:
+            raise ValueError("tile= on a model with fingerprint=%r: the images of a tile batch are tiles, not requests" % (self.fingerprint_mode,))
+
+    def _forward_tiles(self, items, stacked, chunk_forward, *, tile, tile_overlap, tile_batch, seed, stochastic, caption_enc):
+        """Cut -> the ordinary forward over the tile batch in chunks of ``tile_batch`` -> blend.  ``items``: the requests AFTER the input ops
+        (uint8 [H_b, W_b, 3] each); ``chunk_forward(tiles, caption, eps, noise)`` runs one chunk and returns its uint8 outputs.  Noise: every
+        request draws ONE field [lat][ceil(H / 8)][ceil(W / 8)] at (its seed, step 0, stream 0) -- and, stochastic, a second one at stream 2
+        -- and a tile gets the crop at its latent origin (image_ops.tile_cut_planes), so a request's noise depends on neither its slot nor
+        the chunking; without a seed the fields come from torch.randn.  Returns (images, layout)."""
+        from . import image_ops, rng
+        B = len(items)
+        layout = image_ops.tile_layout([t.shape[:2] for t in items], tile, tile_overlap)      # ValueError: the layout rule's refusals
+        seed = seed_argument(seed, B)
+        lat = self.weights.vae_arch.latent_channels
+        with self._on_device():
+            tiles, layout = image_ops.tile_cut_u8(items, tile, tile_overlap, self.lib)
+            crops = []
+            for stream in ((rng.STREAM_EPS, rng.STREAM_NOISE) if stochastic else (rng.STREAM_EPS,)):
+                fields = []
+                for b, (h, w) in enumerate(layout.sizes):
+                    shape = (lat, -(-h // 8), -(-w // 8))
+                    if seed is None:
+                        fields.append(torch.randn(shape, device=self.device_, dtype=torch.float32))
+                    else:
+                        fields.append(rng.randn(shape, seed[b] if isinstance(seed, list) else seed, 0, stream, device=self.device_, lib=self.lib))
+                crops.append(image_ops.tile_cut_planes(fields, layout, self.lib))
+            per_tile = None
+            if caption_enc.dim() == 3 and caption_enc.shape[0] == B and B > 1:               # one caption per request: expanded per tile
+                per_tile = caption_enc.to(self.device_)[torch.tensor(layout.request_of_tile, device=self.device_)]
+            outs = []
+            for k in range(0, layout.T, int(tile_batch)):
+                sl = slice(k, min(k + int(tile_batch), layout.T))
+                outs.append(chunk_forward(tiles[sl], caption_enc if per_tile is None else per_tile[sl], crops[0][sl], crops[1][sl] if stochastic else None))
+            return image_ops.tile_blend_u8(torch.cat(outs) if len(outs) > 1 else outs[0], layout, self.lib, stack=stacked), layout
+
+
+def _bind(names, args, kw):
+    """forward's positional arguments by name, merged with its keywords."""
+    if len(args) > len(names):
+        raise TypeError("forward_u8: %d positional arguments behind the images (at most %d: %s)" % (len(args), len(names), ", ".join(names)))
+    bound = dict(zip(names, args))
+    for k in kw:
+        if k in bound:
+            raise TypeError("forward_u8: %s given twice" % k)
+    bound.update(kw)
+    return bound
+
 
 def seed_argument(seed, B, V=1):
     """``seed=`` of the forwards: None, one int (one noise state for the batch), or a sequence of B ints (one per image) -> None | int | list.
@@ -426,7 +488,8 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         return super().get_plan(B, H, W, *args, _variations=int(variations), **kw)
 
     @torch.no_grad()
-    def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, return_edges=False, resample="lanczos", **kw):
+    def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, return_edges=False, resample="lanczos",
+                   tile=None, tile_overlap=64, tile_batch=8, **kw):
         """uint8 HWC in, uint8 HWC out ([B, H, W, 3] on the device): the callers' ``F.to_tensor`` (src/inference_paired.py:50)
         and ``ToPILImage()(out*0.5+0.5)`` (:72) run inside the boundary kernels; everything else as ``forward``.
         ``resize="multiple_of_8"`` first applies the script's ``input_image.resize((w - w % 8, h - h % 8), Image.LANCZOS)``
@@ -453,7 +516,22 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         ``images_u8`` may also be a LIST of uint8 [H_b, W_b, 3] tensors of different sizes with ``resize=(width, height)``: the requests of a
         batch are brought to the model size in two launches (image_ops.lanczos_resize_u8_ragged) and image b of the result is what the
         stacked, pre-resized batch gives.  A list needs an explicit size: ``resize=None`` / ``"multiple_of_8"`` would leave the images at
-        different sizes in front of the generator (ValueError)."""
+        different sizes in front of the generator (ValueError).
+        ``tile=(tile width, tile height)`` (multiples of 8; NOT part of the reference): a request larger than the model size keeps its size --
+        it is cut into tiles that overlap by ``tile_overlap`` pixels (a multiple of 8, at most half the tile; the layout rule is stated at
+        i2i_tile_request, include/i2i_turbo.h), the tiles run through the ordinary forward in chunks of ``tile_batch`` and the outputs are
+        blended back with an integer feather, cut and blend each one launch on the device.  ``images_u8`` may be a tensor or a list of
+        requests of different sizes (the result is then a list); ``resize=`` applies first.  ``canny=`` runs over the WHOLE request before
+        the cut (hysteresis is not local; ``return_edges=True`` returns ``(out, edges)`` with the requests' shapes), ``sketch=True`` as
+        without tiles.  Noise: with ``seed=`` (one int or one per request) every request draws one field [lat][ceil(H / 8)][ceil(W / 8)] at
+        (seed, step 0) and a tile's eps (and noise map) is the crop at its latent origin, so overlapping tiles see the same noise and a
+        request's noise depends on neither its slot nor the chunking; without ``seed=`` the fields come from torch.randn.  ValueError:
+        ``eps=`` / ``noise_map=``, ``variations`` > 1, per-image health or fingerprints, a request smaller than the tile, a tile that is no
+        multiple of 8, a bad ``tile_overlap``.  Picture quality of tiled output on trained weights is unassessed."""
+        if tile is not None:
+            return self._forward_u8_tiled(images_u8, _bind(("prompt", "prompt_tokens", "deterministic", "r", "noise_map"), args, kw), resize=resize,
+                                          sketch=sketch, canny=canny, return_edges=return_edges, resample=resample, tile=tile,
+                                          tile_overlap=tile_overlap, tile_batch=tile_batch)
         if isinstance(images_u8, (list, tuple)):
             if resize is None or isinstance(resize, str):
                 raise ValueError("a list of images of different sizes needs resize=(width, height): resize=%r leaves them at different sizes" % (resize,))
@@ -478,6 +556,59 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         plan = self._last_plan                   # (the plan that just ran; same stream, so the clones see this run's edge map)
         with self._on_device():
             return (out, plan.canny_edges.clone()) + ((plan.canny_thr.clone(),) if plan.canny_auto else ())
+
+    def _forward_u8_tiled(self, images, opts, *, resize, sketch, canny, return_edges, resample, tile, tile_overlap, tile_batch):
+        """forward_u8 with ``tile=`` (see there): input ops over the whole request, cut, forward over the tile batch, blend."""
+        from . import image_ops
+        unknown = set(opts) - {"prompt", "prompt_tokens", "deterministic", "r", "noise_map", "caption_enc", "eps", "seed", "variations"}
+        if unknown:
+            raise TypeError("forward_u8: unexpected arguments %s" % sorted(unknown))
+        self._tile_refusals(tile, tile_batch, eps=opts.get("eps"), noise_map=opts.get("noise_map"), variations=opts.get("variations", 1))
+        stacked = torch.is_tensor(images)
+        with self._on_device():
+            if resize is not None and not stacked:
+                if isinstance(resize, str):
+                    raise ValueError("a list of images of different sizes takes resize=(width, height), not %r" % (resize,))
+                images, stacked = image_ops.lanczos_resize_u8_ragged(list(images), (int(resize[0]), int(resize[1])), self.lib, resample=resample), True
+            elif resize is not None:
+                images = (image_ops.resize_to_multiple_of_8(images, self.lib, resample=resample) if resize == "multiple_of_8"
+                          else image_ops.lanczos_resize_u8(images, resize, self.lib, resample=resample))
+        items = list(images.unbind(0)) if stacked else list(images)
+        if not items or any(not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != 3 for t in items):
+            raise ValueError("forward_u8(tile=...): uint8 [B, H, W, 3], or a list of uint8 [H, W, 3] requests")
+        image_ops.tile_layout([t.shape[:2] for t in items], tile, tile_overlap)        # the layout rule's refusals, before any device work
+        canny = canny_argument(canny, len(items))
+        if canny is not None and sketch:
+            raise ValueError("canny and sketch=True are the two exclusive branches of the script (src/inference_paired.py:47-58)")
+        if return_edges and canny is None:
+            raise ValueError("return_edges=True needs canny=: without it the input IS the edge map")
+        deterministic = bool(opts.get("deterministic", True))
+        caption_enc = opts.get("caption_enc")
+        if caption_enc is None:
+            assert (opts.get("prompt") is None) != (opts.get("prompt_tokens") is None), "Either prompt or prompt_tokens should be provided"
+            caption_enc = self.encode_prompt(opts.get("prompt"), opts.get("prompt_tokens"))
+        edges = None
+        if canny is not None:                    # Canny over the WHOLE request: hysteresis follows edges across tile borders
+            with self._on_device():
+                edges = []
+                for b, t in enumerate(items):
+                    if canny[0] == "auto" and canny[1][b] is not None:
+                        edges.append(image_ops.canny_u8(t[None], "auto", out_channels=3, lib=self.lib, sigma=canny[1][b])[0])
+                    else:
+                        lows, highs = canny[-2:]
+                        lo, hi = (lows[b], highs[b]) if isinstance(lows, list) else (lows, highs)
+                        edges.append(image_ops.canny_u8(t[None], lo, hi, out_channels=3, lib=self.lib)[0])
+            items = edges
+        u8_io = (1.0, 0.0, 128) if sketch else (1.0, 0.0)
+
+        def chunk(tiles, cap, eps, noise):
+            return self.forward(tiles, deterministic=deterministic, r=opts.get("r", 1.0), noise_map=noise, caption_enc=cap, eps=eps, _u8_io=u8_io)
+
+        out, _ = self._forward_tiles(items, stacked, chunk, tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch, seed=opts.get("seed"),
+                                     stochastic=not deterministic, caption_enc=caption_enc)
+        if not return_edges:
+            return out
+        return out, (torch.stack(edges) if stacked else edges)
 
     @torch.no_grad()
     def forward(self, c_t, prompt=None, prompt_tokens=None, deterministic=True, r=1.0, noise_map=None,

@@ -59,7 +59,8 @@ _WRITES = {K.OP_IGEMM: ("c", "c2", "ws", "gn_part"), K.OP_GN_STATS: ("partial", 
            K.OP_CANNY_U8: ("dst", "ws"), K.OP_RANDN: ("dst", "state"), K.OP_TWIN_FOLD: ("dst", "bias"), K.OP_SCAN: ("rec",),
            K.OP_RANDN_BATCH: ("dst", "states"), K.OP_CANNY_U8_BATCH: ("dst", "ws"), K.OP_RESIZE_U8_RAGGED: ("dst", "bad_mask"),
            K.OP_SCAN_BATCH: ("rec",), K.OP_SCAN_VERDICT: ("rec", "verdict"), K.OP_CANNY_AUTO_THR: ("thr", "median2", "ws"), K.OP_DIGEST: ("rec",),
-           K.OP_REPEAT: tuple("dst%d" % s for s in range(K.REPEAT_MAX_SEGMENTS))}
+           K.OP_REPEAT: tuple("dst%d" % s for s in range(K.REPEAT_MAX_SEGMENTS)), K.OP_TILE_CUT: ("dst", "bad_mask"),
+           K.OP_TILE_BLEND_U8: ("dst", "bad_mask")}
 
 
 def _pointer_fields():

@@ -65,7 +65,9 @@ typedef enum {
     I2I_OP_SCAN_VERDICT = 23,
     I2I_OP_CANNY_AUTO_THR = 24,    /* ABI 14 addition (see the note above i2i_canny_auto_thr_params) */
     I2I_OP_DIGEST = 25,            /* ABI 14 addition (see the note above i2i_digest_params) */
-    I2I_OP_REPEAT = 26             /* ABI 14 addition (see the note above i2i_repeat_params) */
+    I2I_OP_REPEAT = 26,            /* ABI 14 addition (see the note above i2i_repeat_params) */
+    I2I_OP_TILE_CUT = 27,          /* ABI 14 additions (see the note above i2i_tile_request) */
+    I2I_OP_TILE_BLEND_U8 = 28
 } i2i_opcode;
 
 /* ---------------------------------------------------------------------------------------------
@@ -675,6 +677,92 @@ typedef struct {
     i2i_repeat_segment seg[I2I_REPEAT_MAX_SEGMENTS];      /* entries from n_segments on are ignored (keep them zero in a plan file) */
 } i2i_repeat_params;
 
+/* ---- ABI 14 addition: tiled forward at native resolution (I2I_OP_TILE_CUT, I2I_OP_TILE_BLEND_U8).  Purely additive like the ones above -- two
+ * new opcodes, three new structs, three new exported functions; no existing struct, opcode number or signature changed and sizeof(i2i_op)
+ * did not grow -- so I2I_ABI_VERSION stays 14.  A library built before the addition is recognised by the missing symbols (i2i_tile_cut,
+ * i2i_tile_blend_u8, i2i_tile_positions), and its plan loader refuses the new opcodes as unknown.
+ *
+ * A request larger than the model size is cut into overlapping tiles of the model size, the tiles run through the ordinary forward as one
+ * batch, and the tile outputs are blended back with a linear feather.  Tiling is NOT part of the reference (its scripts resize the request
+ * to the model size, src/inference_unpaired.py:40,53); it sits where variations= and the automatic Canny thresholds sit.
+ *
+ * THE LAYOUT RULE (i2i_tile_positions, one axis of length L, tile extent t, overlap ov):
+ *   conditions  t > 0, t % 8 == 0, ov % 8 == 0, 0 <= ov <= t / 2, L >= t
+ *   stride      s = t - ov;  count n = 1 + ceil((L - t) / s);  positions x_k = min(k * s, L - t), k = 0 .. n - 1
+ * The first tile starts at 0, the last ends at L, positions increase strictly, neighbours overlap by at least ov, every position but the
+ * last is a multiple of 8, every pixel is covered by 1 .. 3 tiles per axis, and x_k / 8 + t / 8 <= ceil(L / 8) (integer division): the
+ * crop of a [ceil(L / 8)] latent-resolution field at x_k / 8 stays inside it.  1280, 512, 64 -> {0, 448, 768};  34, 16, 8 -> {0, 8, 16, 18}.
+ * The tiles of a request are numbered row-major (ky outer, kx inner); the tiles of request b follow those of request b - 1.
+ * i2i_tile_positions: plain host code, no GPU.  Returns n and writes n positions to `out`; out == NULL only counts.  I2I_ERR_BAD_ARG
+ * (nothing written) for arguments outside the conditions or capacity < n.  Bit-equal to image_ops.tile_positions.
+ *
+ * REQUEST b  reqs[b] (i2i_tile_request, 48 bytes, device memory), shared by both ops: the request's pixels are dense
+ *            [planes][h][w] pixels of px_bytes bytes at arena + off (uint8 HWC images: planes = 1, px_bytes = c; fp32 planar fields:
+ *            px_bytes = 4), its nx * ny tiles occupy the tile slots tile0 .. tile0 + nx * ny - 1 (slot tile0 + ky * nx + kx has its origin at
+ *            (ys[ky], xs[kx])), xs[nx] at pos + xs_off and ys[ny] at pos + ys_off.  h == 0 or w == 0 is an EMPTY SLOT: nothing else of it is
+ *            read, nothing is written.
+ * GRID       a function of n and grid_units ONLY (grid y = request, min(ceil(grid_units / 1024), 1024) workgroups of 256 per request in x,
+ *            each striding over the request's rows), so a captured graph stays valid when the host rewrites descriptors, positions and
+ *            pixels in place.  grid_units is a capacity hint -- the largest number of tile-batch dwords (cut) / image bytes (blend) any
+ *            request will have; results do not depend on it (1 is correct, only slow).
+ * SAFETY     Before touching a pixel every workgroup checks its request: h, w, nx, ny positive; off non-negative, a multiple of 4 and the
+ *            request's planes * h * w * px_bytes bytes inside arena_bytes; xs_off / ys_off non-negative with nx / ny elements inside
+ *            pos_len; tile0 >= 0 and tile0 + nx * ny <= tiles_capacity; every position 0 <= x and x + tw <= w (0 <= y, y + th <= h).
+ *            i2i_tile_blend_u8 also wants the positions of an axis strictly increasing with xs[k + 3] >= xs[k] + tw (at most 3 tiles over a
+ *            pixel per axis, 9 in 2-D: what the layout rule gives).  A request that fails is SKIPPED as a whole (its destination bytes
+ *            stay as they were) and bit (b & 31) is OR-ed into *bad_mask (if given; the owner zeroes it); the other requests are
+ *            unaffected.  A wrong descriptor is a flag, never a fault.  Requests must not share tile slots; the arena and the tile batch must
+ *            not overlap.
+ *
+ * i2i_tile_cut: tiles[slot][planes][th][tw] = the request's [planes][y0 .. y0 + th)[x0 .. x0 + tw), ONE launch for every tile of every
+ * request: pure byte movement, bit-equal to slicing.  Dword stores (and dword loads: one where the source is aligned, the enclosing aligned
+ * pair where it is not, bytes at the arena's last dword) when tw * px_bytes is a multiple of 4, byte access otherwise, chosen at run time.
+ * The noise rule of a tiled forward is this op on fp32 fields: a request draws ONE field [lat][ceil(h / 8)][ceil(w / 8)] and the eps of the
+ * tile at (y0, x0) is its crop at (y0 / 8, x0 / 8) -- descriptors with extents ceil(. / 8), positions / 8 and a tile of (tw / 8, th / 8).
+ *
+ * i2i_tile_blend_u8: the inverse.  tiles[slot][th][tw][c] uint8 -> every request's [h][w][c] at arena + off, GATHER form: one thread owns
+ * output bytes and sums over the tiles that cover them -- no atomics, the result does not depend on grid or scheduling.  INTEGER CONTRACT:
+ *   weight of tile pixel (i, j):  w = wx(i) * wy(j),  wx(i) = min(i + 1, tw - i, ramp),  wy(j) = min(j + 1, th - j, ramp),  1 <= ramp <= 256
+ *   over the covering tiles:      num = sum w * u8,  den = sum w;   out = (2 * num + den) / (2 * den)   (integer division: rounds half up)
+ * A weight is never zero, so image borders and the wider overlap of a last tile come out right by the normalisation alone; ramp = 1 is the
+ * plain average of the covering tiles, overlap 0 a plain paste; blend(cut(img)) == img.  The accumulators are uint32: at most 9 covering
+ * tiles (the check above) of weight <= ramp^2 <= 2^16 give 2 * num + den <= 9 * 2^16 * 511 < 2^32.  A pixel that NO tile covers is written
+ * as 0 and its request's bit is set in *bad_mask (the request is still written; the layout rule never produces one).
+ * Both: one launch, no allocation, no synchronisation, no read-back; graph-capturable.  n == 0 is a successful no-op.
+ * Errors (I2I_ERR_BAD_ARG, the message names the field): null params; n < 0; planes < 1; px_bytes / c outside 1..4; tw / th < 1;
+ * tiles_capacity < 0; ramp outside 1..256; grid_units < 1; negative arena_bytes / pos_len; (n > 0) arena / tiles / reqs / pos null, arena /
+ * tiles / pos / bad_mask not 4-byte aligned, reqs not 8-byte aligned. */
+typedef struct {                       /* device, one per request, 48 bytes */
+    int64_t off;                       /* byte offset of the request's pixels in the arena, a multiple of 4 */
+    int32_t h, w;                      /* extent in pixels; h == 0 or w == 0: empty slot */
+    int32_t tile0;                     /* first tile slot of the request */
+    int32_t nx, ny;                    /* tiles per row / per column */
+    int32_t xs_off, ys_off;            /* int32-element offsets into `pos` */
+    int32_t reserved[3];               /* ignored */
+} i2i_tile_request;
+typedef struct {
+    const void* src; void* dst;        /* the request arena; the tile batch [tiles_capacity][planes][th][tw] pixels; both 4-byte aligned */
+    int64_t arena_bytes;               /* capacity of src */
+    const i2i_tile_request* reqs;      /* device [n] */
+    const int32_t* pos; int64_t pos_len;   /* device int32 pool of positions and its length in elements */
+    int32_t n, planes, px_bytes;       /* px_bytes 1..4 */
+    int32_t tw, th;                    /* tile extent in pixels */
+    int32_t tiles_capacity;            /* tile slots dst holds */
+    int64_t grid_units;                /* capacity hint that sizes the grid ONLY (>= 1) */
+    uint32_t* bad_mask;                /* optional device word */
+} i2i_tile_cut_params;
+typedef struct {
+    const void* tiles; void* dst;      /* the tile batch [tiles_capacity][th][tw][c] uint8; the request arena; both 4-byte aligned */
+    int64_t arena_bytes;               /* capacity of dst */
+    const i2i_tile_request* reqs;      /* device [n]: the descriptors of the cut with planes = 1, px_bytes = c */
+    const int32_t* pos; int64_t pos_len;
+    int32_t n, c, ramp;                /* c 1..4; ramp 1..256 (the model classes pass max(overlap, 1)) */
+    int32_t tw, th;
+    int32_t tiles_capacity;
+    int64_t grid_units;
+    uint32_t* bad_mask;
+} i2i_tile_blend_u8_params;
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -707,6 +795,8 @@ typedef struct {
         i2i_canny_auto_thr_params canny_auto_thr;
         i2i_digest_params digest;
         i2i_repeat_params repeat;
+        i2i_tile_cut_params tile_cut;
+        i2i_tile_blend_u8_params tile_blend_u8;
     } u;
 } i2i_op;
 
@@ -752,6 +842,10 @@ int i2i_canny_auto_thr(const i2i_canny_auto_thr_params* p, int dtype, void* stre
 size_t i2i_canny_auto_ws_bytes(int n);                                                 /* bytes of i2i_canny_auto_thr_params.ws (0 for n < 1) */
 int i2i_digest(const i2i_digest_params* p, int dtype, void* stream);                   /* one launch; dtype = element type of x (I2I_U8 allowed) */
 int i2i_repeat(const i2i_repeat_params* p, int dtype, void* stream);                   /* dtype ignored (bytes); one launch */
+int i2i_tile_cut(const i2i_tile_cut_params* p, int dtype, void* stream);               /* dtype ignored (bytes); one launch */
+int i2i_tile_blend_u8(const i2i_tile_blend_u8_params* p, int dtype, void* stream);     /* dtype ignored (uint8 data); one launch */
+/* The tile positions of one axis (the layout rule above i2i_tile_request): host code, returns the count or I2I_ERR_BAD_ARG. */
+int i2i_tile_positions(int L, int t, int ov, int32_t* out, int capacity);
 /* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
  * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
  * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
