@@ -197,6 +197,21 @@ class TileBlendU8Params(C.Structure):
                 ("ramp", i32), ("tw", i32), ("th", i32), ("tiles_capacity", i32), ("grid_units", i64), ("bad_mask", vp)]
 
 
+class JpegImage(C.Structure):
+    """One image of a JPEG encode (i2i_jpeg_image, 48 bytes, lives in DEVICE memory: image_ops.JPEG_IMAGE_DTYPE packs it)."""
+    _fields_ = [("src_off", i64), ("dst_off", i64), ("h", i32), ("w", i32), ("c", i32), ("quality", i32), ("subsampling", i32), ("capacity", i32),
+                ("reserved", i32 * 2)]
+
+
+class JpegEncodeU8Params(C.Structure):
+    """i2i_jpeg_encode_u8_params: an eager entry, not a member of i2i_op (no opcode)."""
+    _fields_ = [("src", vp), ("src_bytes", i64), ("dst", vp), ("dst_bytes", i64), ("images", vp), ("length", vp), ("bad_mask", vp), ("ws", vp),
+                ("ws_bytes", i64), ("n", i32), ("reserved", i32), ("max_blocks", i64)]
+
+
+JPEG_HEADER_BYTES = 623
+
+
 class NopParams(C.Structure):
     _fields_ = [("unused", i32)]
 
@@ -233,7 +248,7 @@ EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", 
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
            "i2i_plan_has_scale", "i2i_plan_set_scale", "i2i_digest", "i2i_plan_verify", "i2i_repeat",
-           "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_tile_positions"]
+           "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_tile_positions", "i2i_jpeg_encode_u8", "i2i_jpeg_workspace_bytes", "i2i_jpeg_header"]
 
 
 class I2IError(RuntimeError):
@@ -287,7 +302,7 @@ class Library:
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
                      "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
                      "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr", "i2i_digest", "i2i_repeat",
-                     "i2i_tile_cut", "i2i_tile_blend_u8"):
+                     "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_jpeg_encode_u8"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -300,6 +315,10 @@ class Library:
         L.i2i_resample_tables.restype = C.c_int
         L.i2i_tile_positions.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int]
         L.i2i_tile_positions.restype = C.c_int
+        L.i2i_jpeg_workspace_bytes.argtypes = [C.c_int, C.c_int64]
+        L.i2i_jpeg_workspace_bytes.restype = C.c_size_t
+        L.i2i_jpeg_header.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        L.i2i_jpeg_header.restype = C.c_int
         L.i2i_lanczos_ksize.argtypes = [C.c_int, C.c_int]
         L.i2i_lanczos_ksize.restype = C.c_int
         L.i2i_lanczos_tables.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int]
@@ -369,6 +388,16 @@ class Library:
         out = (C.c_int32 * n)()
         self.check(min(int(self.lib.i2i_tile_positions(int(length), int(tile), int(overlap), C.addressof(out), n)), 0))
         return list(out)
+
+    def jpeg_workspace_bytes(self, n, max_blocks):
+        """Bytes of the workspace i2i_jpeg_encode_u8 needs for n images of at most ``max_blocks`` 8 x 8 blocks each."""
+        return int(self.lib.i2i_jpeg_workspace_bytes(int(n), int(max_blocks)))
+
+    def jpeg_header(self, quality, subsampling, w, h):
+        """The 623 bytes i2i_jpeg_encode_u8 writes in front of the scan (i2i_jpeg_header, host code); ``subsampling``: 0 or 2."""
+        out = (C.c_uint8 * JPEG_HEADER_BYTES)()
+        self.check(min(int(self.lib.i2i_jpeg_header(int(quality), int(subsampling), int(w), int(h), C.addressof(out))), 0))
+        return bytes(out)
 
     def lanczos_tables(self, in_size, out_size, ksize_capacity=None):
         """The library's own tap tables (i2i_lanczos_tables, host code): (ksize, bounds int32 [out, 2], coeffs int32 [out, capacity]) as numpy

@@ -30,6 +30,8 @@ def _split(src):
         return f, ["-DW32_PART=" + n], f.replace(".hip", "_p%s.o" % n)
     return src, [], src.replace(".hip", ".o")
 HEADERS = ["i2i_dev.h", "launch.h", os.path.join("..", "..", "include", "i2i_turbo.h")]
+# source text a single .hip file includes (not a translation unit of its own): part of that object's digest and of the library's
+INCLUDES = {"resize.hip": ["jpeg.inc"]}
 LIB = os.path.join(HERE, "libi2i_turbo.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 # per-source flags.  conv3x3_w32 / gemm_w32: VALU work runs in the MFMA shadow at one wave per SIMD, where packed-f32
@@ -64,12 +66,12 @@ def _record(path, digest):
 def source_digest(src, defs=()):
     """What an object depends on: its source, the shared headers, the flags."""
     f, part, _ = _split(src)
-    return _digest([os.path.join(HERE, f)] + [os.path.join(HERE, h) for h in HEADERS], FLAGS + EXTRA_FLAGS.get(f, []) + part + list(defs))
+    return _digest([os.path.join(HERE, f)] + [os.path.join(HERE, h) for h in INCLUDES.get(f, []) + HEADERS], FLAGS + EXTRA_FLAGS.get(f, []) + part + list(defs))
 
 
 def library_digest(defs=()):
     files = sorted({_split(s)[0] for s in SOURCES})
-    return _digest([os.path.join(HERE, f) for f in files] + [os.path.join(HERE, h) for h in HEADERS],
+    return _digest([os.path.join(HERE, f) for f in files] + [os.path.join(HERE, h) for f in files for h in INCLUDES.get(f, [])] + [os.path.join(HERE, h) for h in HEADERS],
                    FLAGS + [EXTRA_FLAGS.get(_split(s)[0], []) + _split(s)[1] for s in SOURCES] + list(defs))
 
 

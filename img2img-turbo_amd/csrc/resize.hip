@@ -1056,3 +1056,7 @@ extern "C" int i2i_tile_blend_u8(const i2i_tile_blend_u8_params* p, int dtype, v
     hipLaunchKernelGGL(tile_blend_u8_kernel, tile_grid(p->n, p->grid_units), dim3(256), 16, (hipStream_t)stream, *p);
     return i2i::check_launch("tile_blend_u8");
 }
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Baseline JPEG encoding, the last uint8 boundary op (i2i_jpeg_encode_u8, i2i_jpeg_workspace_bytes, i2i_jpeg_header)
+#include "jpeg.inc"

@@ -46,7 +46,8 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         self.vae_enc._model = self.vae_dec._model = self.unet._model = self
 
     @torch.no_grad()
-    def forward_u8(self, images_u8, *args, resize=None, resize_back=False, image_prep=None, tile=None, tile_overlap=64, tile_batch=8, **kw):
+    def forward_u8(self, images_u8, *args, resize=None, resize_back=False, image_prep=None, tile=None, tile_overlap=64, tile_batch=8, jpeg=None,
+                   **kw):
         """uint8 HWC in/out on the device: ``Normalize([0.5],[0.5])(to_tensor(img))`` (src/inference_unpaired.py:47) and
         ``ToPILImage()(out*0.5+0.5)`` (:53) run inside the boundary kernels.  ``resize=(width, height)`` applies the script's
         ``transforms.Resize(..., LANCZOS)`` (:40-47, e.g. (512, 512) for "resize_512x512") before the generator and
@@ -60,7 +61,18 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         ``tile=(tile width, tile height)`` with ``tile_overlap`` / ``tile_batch``: the request keeps its size and runs as overlapping tiles
         of the model size, cut and feather-blended on the device, as Pix2Pix_Turbo.forward_u8 describes (noise rule, refusals and the
         caveat on picture quality included); ``resize=`` / ``image_prep=`` apply first, ``resize_back=True`` is refused, and a list of
-        requests of different sizes needs no common size."""
+        requests of different sizes needs no common size.
+        ``jpeg=True`` / a quality / ``(quality, "4:4:4" | "4:2:0")`` / a list of one such entry per image: the script's
+        ``output_pil.save(...)`` (src/inference_unpaired.py:58) on the device, as Pix2Pix_Turbo.forward_u8 describes -- a list of ``bytes``,
+        byte-identical to Pillow's files; with ``resize_back=True`` or ``tile=`` on a list every request is encoded at its own size."""
+        if jpeg is not None:
+            from . import image_ops
+            n = images_u8.shape[0] if torch.is_tensor(images_u8) else len(images_u8)
+            spec = image_ops.jpeg_argument(jpeg, n)
+            res = self.forward_u8(images_u8, *args, resize=resize, resize_back=resize_back, image_prep=image_prep, tile=tile, tile_overlap=tile_overlap,
+                                  tile_batch=tile_batch, **kw)
+            with self._on_device():
+                return image_ops.jpeg_files(res, spec, self.lib)
         if tile is not None:
             return self._forward_u8_tiled(images_u8, _bind(("direction", "caption", "caption_emb"), args, kw), resize=resize, resize_back=resize_back,
                                           image_prep=image_prep, tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch)

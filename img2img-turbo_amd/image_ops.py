@@ -466,6 +466,129 @@ def tile_blend_u8(tiles, layout, lib=None, *, ramp=None, stack=False):
     return dst[:len(views) * h * w * c].view(len(views), h, w, c) if (h * w * c) % 4 == 0 and len(set(layout.sizes)) == 1 else torch.stack(views)
 
 
+# ---- JPEG files on the device: i2i_jpeg_encode_u8 (include/i2i_turbo.h), five launches for any number of images of any sizes ----
+JPEG_IMAGE_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("c", "<i4"), ("quality", "<i4"), ("subsampling", "<i4"),
+                             ("capacity", "<i4"), ("reserved", "<i4", (2,))])
+assert JPEG_IMAGE_DTYPE.itemsize == 48
+JPEG_SUBSAMPLINGS = {"4:4:4": 0, "4:2:0": 2, 0: 0, 2: 2}     # the names and Pillow's numbers
+
+
+def jpeg_blocks(h, w, subsampling):
+    """8 x 8 blocks of an image in scan order, dummy blocks included (the unit of i2i_jpeg_encode_u8's capacity hint)."""
+    if JPEG_SUBSAMPLINGS[subsampling] == 2:
+        return 6 * (-(-h // 16)) * (-(-w // 16))
+    return 3 * (-(-h // 8)) * (-(-w // 8))
+
+
+def jpeg_capacity(h, w, subsampling):
+    """Default bytes reserved for one file: header, EOI and 128 bytes per block, i.e. two bytes per sample.  Uniform noise and random 0 / 255
+    pixels at quality 100 need up to 102 bytes per block (tests/jpeg_ref.py), twice what 3 bytes per pixel holds for 4:4:4; the hard bound
+    of the format is 416 (1660 bits per block, every byte stuffed), which a caller who needs it passes as ``capacity=``."""
+    return _capi.JPEG_HEADER_BYTES + 2 + 128 * jpeg_blocks(h, w, subsampling)
+
+
+def _per_image(value, n, what):
+    vals = list(value) if isinstance(value, (list, tuple)) else [value] * n
+    if len(vals) != n:
+        raise ValueError("jpeg_encode_u8: %d %s for %d images" % (len(vals), what, n))
+    return vals
+
+
+def jpeg_encode_u8(images, quality=75, subsampling="4:2:0", *, capacity=None, lib=None, return_tensors=False, max_blocks=None):
+    """Baseline JPEG files of a batch, byte-identical to ``Image.fromarray(x).save(f, "JPEG", quality=, subsampling=)`` of Pillow with
+    libjpeg-turbo (i2i_jpeg_encode_u8: five launches whatever the batch holds).  ``images``: a uint8 [B, H, W, C] tensor or a list of uint8
+    [H_b, W_b, C] tensors of different sizes on one device, C = 3 or 1 (grey, replicated); ``quality`` (1 .. 100) and ``subsampling``
+    ("4:4:4" / "4:2:0", or Pillow's 0 / 2): one value or one per image; the defaults are Pillow's.  ``capacity``: bytes reserved per file
+    (one value or one per image; default jpeg_capacity).  ``max_blocks``: the capacity hint that sizes grids and workspace (default: the
+    largest image's blocks; results do not depend on it).  Returns a list of ``bytes`` after ONE synchronisation and ONE copy of the used
+    bytes; an image that was flagged (its file does not fit its capacity) raises I2IError naming its index.  ``return_tensors=True``:
+    (pool uint8, offsets list, lengths int32 [B] on the device, bad_mask int32 [1]) without any synchronisation."""
+    lib = lib or _capi.default_library()
+    items = _request_list(images, "jpeg_encode_u8")
+    n, dev = len(items), items[0].device
+    c = int(items[0].shape[-1]) if items[0].dim() == 3 else 0
+    if c not in (1, 3) or any(t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != c or t.device != dev for t in items):
+        raise ValueError("jpeg_encode_u8: uint8 [H, W, C] images that share the channel count (3 or 1) and the device")
+    if any(not (1 <= t.shape[0] <= 65535 and 1 <= t.shape[1] <= 65535) for t in items):
+        raise ValueError("jpeg_encode_u8: image extents must be 1 .. 65535")
+    assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
+    quals = [int(q) for q in _per_image(quality, n, "qualities")]
+    try:
+        subs = [JPEG_SUBSAMPLINGS[s] for s in _per_image(subsampling, n, "subsamplings")]
+    except (KeyError, TypeError):
+        raise ValueError("jpeg_encode_u8: subsampling must be \"4:4:4\" or \"4:2:0\" (0 or 2), got %r" % (subsampling,))
+    sizes = [(int(t.shape[0]), int(t.shape[1])) for t in items]
+    caps = [jpeg_capacity(h, w, s) for (h, w), s in zip(sizes, subs)] if capacity is None else [int(v) for v in _per_image(capacity, n, "capacities")]
+    blocks = max(jpeg_blocks(h, w, s) for (h, w), s in zip(sizes, subs))
+    max_blocks = blocks if max_blocks is None else int(max_blocks)
+    desc = np.zeros(n, dtype=JPEG_IMAGE_DTYPE)
+    src_off = dst_off = 0
+    offsets = []
+    for b, ((h, w), q, s, cap) in enumerate(zip(sizes, quals, subs, caps)):
+        desc[b] = (src_off, dst_off, h, w, c, q, s, cap, (0, 0))
+        offsets.append(dst_off)
+        src_off += _align4(h * w * c)
+        dst_off += cap
+    from . import ops as O
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        src = _pack_arena(items)
+        if src.data_ptr() % 4:
+            src = src.clone()
+        desc_dev = torch.from_numpy(desc.view(np.int64).reshape(-1).copy()).to(dev)
+        pool = torch.empty(max(dst_off, 4), dtype=torch.uint8, device=dev)
+        state = torch.zeros(n + 1, dtype=torch.int32, device=dev)               # lengths [n], then the flag word
+        ws = torch.empty(max(lib.jpeg_workspace_bytes(n, max_blocks), 16), dtype=torch.uint8, device=dev)
+        p = O.jpeg_encode_u8(src, pool, desc_dev, state, ws, n=n, max_blocks=max_blocks, bad_mask=state[n:], dst_bytes=dst_off)
+        lib.check(lib.lib.i2i_jpeg_encode_u8(C.addressof(p), 0, stream))
+    if return_tensors:
+        return pool, offsets, state[:n], state[n:]
+    host = state.cpu().numpy()                                                   # the one synchronisation
+    lengths = host[:n].astype(np.int64)
+    bad = [b for b in range(n) if lengths[b] == 0]
+    if bad or host[n]:
+        raise _capi.I2IError("jpeg_encode_u8: image %d does not fit its capacity of %d bytes (or its descriptor was refused); flagged: %s"
+                             % (bad[0] if bad else -1, caps[bad[0]] if bad else 0, bad))
+    if n == 1 or int(lengths.sum()) * 2 >= dst_off:
+        used = pool[:offsets[-1] + int(lengths[-1])].cpu().numpy()
+        return [used[o:o + int(l)].tobytes() for o, l in zip(offsets, lengths)]
+    idx = torch.cat([torch.arange(o, o + int(l), device=dev) for o, l in zip(offsets, lengths)])   # the used bytes only, one copy
+    used = pool[idx].cpu().numpy()
+    ends = np.cumsum(lengths)
+    return [used[e - l:e].tobytes() for e, l in zip(ends, lengths)]
+
+
+def jpeg_argument(jpeg, n, variations=1):
+    """``jpeg=`` of the models' forward_u8 -> (qualities, subsamplings), one per output file (n inputs x V variations, image-major).
+    ``True``: Pillow's defaults (75, "4:2:0"); an int: the quality; ``(quality, subsampling)``; a LIST of n such entries, one per input."""
+    def one(e):
+        if e is True:
+            return 75, 2
+        if isinstance(e, tuple) and len(e) == 2:
+            q, s = e
+        else:
+            q, s = e, "4:2:0"
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or isinstance(s, bool) or s not in JPEG_SUBSAMPLINGS:
+            raise ValueError("jpeg=%r: True, a quality (int), (quality, \"4:4:4\" | \"4:2:0\"), or a list of one such entry per image" % (jpeg,))
+        return int(q), JPEG_SUBSAMPLINGS[s]
+    if isinstance(jpeg, list):
+        if len(jpeg) != n:
+            raise ValueError("jpeg= holds %d entries for %d images" % (len(jpeg), n))
+        entries = [one(e) for e in jpeg for _ in range(variations)]
+    else:
+        entries = [one(jpeg)] * (n * variations)
+    return [q for q, _ in entries], [s for _, s in entries]
+
+
+def jpeg_files(result, spec, lib):
+    """What forward_u8 returned (the uint8 images, or a tuple that starts with them) with the images replaced by their JPEG files."""
+    rest = ()
+    if isinstance(result, tuple):
+        result, rest = result[0], result[1:]
+    files = jpeg_encode_u8(result, spec[0], spec[1], lib=lib)
+    return (files,) + rest if rest else files
+
+
 def canny_thresholds(low, high):
     """The two ints the kernels compare against: float thresholds floored (the magnitudes are integers, so ``mag > floor(t)`` is
     ``mag > t``); the kernels swap them if low > high."""

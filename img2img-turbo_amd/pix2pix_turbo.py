@@ -489,7 +489,7 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
 
     @torch.no_grad()
     def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, return_edges=False, resample="lanczos",
-                   tile=None, tile_overlap=64, tile_batch=8, **kw):
+                   tile=None, tile_overlap=64, tile_batch=8, jpeg=None, **kw):
         """uint8 HWC in, uint8 HWC out ([B, H, W, 3] on the device): the callers' ``F.to_tensor`` (src/inference_paired.py:50)
         and ``ToPILImage()(out*0.5+0.5)`` (:72) run inside the boundary kernels; everything else as ``forward``.
         ``resize="multiple_of_8"`` first applies the script's ``input_image.resize((w - w % 8, h - h % 8), Image.LANCZOS)``
@@ -527,7 +527,20 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         (seed, step 0) and a tile's eps (and noise map) is the crop at its latent origin, so overlapping tiles see the same noise and a
         request's noise depends on neither its slot nor the chunking; without ``seed=`` the fields come from torch.randn.  ValueError:
         ``eps=`` / ``noise_map=``, ``variations`` > 1, per-image health or fingerprints, a request smaller than the tile, a tile that is no
-        multiple of 8, a bad ``tile_overlap``.  Picture quality of tiled output on trained weights is unassessed."""
+        multiple of 8, a bad ``tile_overlap``.  Picture quality of tiled output on trained weights is unassessed.
+        ``jpeg=True`` / a quality / ``(quality, "4:4:4" | "4:2:0")`` / a list of one such entry per input image: the script's
+        ``output_pil.save(...)`` (src/inference_paired.py:75) on the device -- the images come back as a list of ``bytes``, each the complete
+        baseline JPEG file Pillow writes for that image at that quality and subsampling, byte for byte (image_ops.jpeg_encode_u8; ``True`` is
+        Pillow's default, quality 75 at 4:2:0), in the order the tensor would have had (``variations=V``: image-major, B * V files; ``tile=``
+        or a list: every request at its own size, one ragged call).  ``return_edges=True`` keeps returning the edges beside them."""
+        if jpeg is not None:
+            from . import image_ops
+            n = images_u8.shape[0] if torch.is_tensor(images_u8) else len(images_u8)
+            spec = image_ops.jpeg_argument(jpeg, n, int(kw.get("variations", 1)))
+            res = self.forward_u8(images_u8, *args, resize=resize, sketch=sketch, canny=canny, return_edges=return_edges, resample=resample, tile=tile,
+                                  tile_overlap=tile_overlap, tile_batch=tile_batch, **kw)
+            with self._on_device():
+                return image_ops.jpeg_files(res, spec, self.lib)
         if tile is not None:
             return self._forward_u8_tiled(images_u8, _bind(("prompt", "prompt_tokens", "deterministic", "r", "noise_map"), args, kw), resize=resize,
                                           sketch=sketch, canny=canny, return_edges=return_edges, resample=resample, tile=tile,

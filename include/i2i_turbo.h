@@ -763,6 +763,70 @@ typedef struct {
     uint32_t* bad_mask;
 } i2i_tile_blend_u8_params;
 
+/* ---- ABI 14 addition: baseline JPEG encoding of a ragged uint8 batch on the device (i2i_jpeg_encode_u8, i2i_jpeg_workspace_bytes,
+ * i2i_jpeg_header).  Purely additive -- two new structs, three new exported functions, NO opcode (the entry is an eager call on the
+ * caller's stream, graph-capturable; plan files do not carry it) and i2i_op is untouched -- so I2I_ABI_VERSION stays 14.  A library built
+ * before the addition is recognised by the missing symbols.
+ *
+ * The last host line of the reference's scripts is output_pil.save(...) (src/inference_paired.py:75, src/inference_unpaired.py:58).  This
+ * entry writes, per image, the COMPLETE FILE Pillow with libjpeg-turbo writes for Image.save(f, "JPEG", quality=q, subsampling=s), byte
+ * for byte (tests/jpeg_ref.py is the integer restatement the tests pin against the installed Pillow).  THE RULES, all integer:
+ *   header    623 bytes: SOI, APP0 JFIF 1.01 (units 0, density 1 x 1, no thumbnail), DQT 0, DQT 1 (8-bit, zigzag order), SOF0 (precision 8,
+ *             h, w, components 1, 2, 3 with sampling 0x22 (4:2:0) or 0x11 (4:4:4) for Y and 0x11 for Cb, Cr, tables 0, 1, 1), DHT DC0, AC0,
+ *             DC1, AC1 (the typical tables of ITU-T T.81 Annex K.3), SOS (three components, selectors 0x00, 0x11, 0x11, Ss 0, Se 63, 0).
+ *   tables    Annex K.1 scaled by s = 5000 / q (q < 50) or 200 - 2 q, entry (t * s + 50) / 100 clamped to 1 .. 255; q clamped to 1 .. 100.
+ *   colour    Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *             Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16;  Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   padding   columns replicate the last input column, rows of Y (and of 4:4:4 chroma) the last input row; for 4:2:0 the input is padded to
+ *             an even height, downsampled as (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, .. along a row, and the DOWNSAMPLED plane's last
+ *             row is replicated.
+ *   DCT       libjpeg's jfdctint ("islow", CONST_BITS 13, PASS1_BITS 2) on samples - 128, rows then columns.
+ *   quantise  d = 8 * table entry;  (|c| + (d >> 1)) / d with the sign restored.
+ *   scan      one interleaved scan, MCU = Y Cb Cr (4:4:4) or Y00 Y01 Y10 Y11 Cb Cr (4:2:0).  A Y block of a 4:2:0 MCU beyond ceil(w / 8)
+ *             columns or ceil(h / 8) rows is a DUMMY block: no AC coefficients, the DC of the block before it in the MCU.  DC differences
+ *             per component, ZRL per 16 zeros, EOB when a block ends in zeros, bits packed MSB first, the last byte padded with 1-bits, 0x00
+ *             stuffed after every 0xFF byte of the scan, then EOI.
+ * IMAGE b    images[b] (i2i_jpeg_image, 48 bytes, DEVICE memory): dense [h][w][c] uint8 pixels at src + src_off, c = 3 (RGB) or 1 (grey,
+ *            replicated into the three channels as convert("RGB") does).  The file goes to dst + dst_off (any alignment), at most `capacity`
+ *            bytes; length[b] receives its size.  Sizes, quality and subsampling are DEVICE STATE: a captured graph serves every quality
+ *            and every set of sizes whose blocks fit max_blocks.
+ * GRID       a function of n and max_blocks only.  max_blocks is the capacity hint: the largest number of 8 x 8 blocks in scan order (dummy
+ *            blocks included: 3 * ceil(w / 8) * ceil(h / 8) for 4:4:4, 6 * ceil(w / 16) * ceil(h / 16) for 4:2:0) any image will have.  It
+ *            sizes the grids and the per-image slot of the workspace (i2i_jpeg_workspace_bytes(n, max_blocks)); results do not depend on it.
+ * SAFETY     Every workgroup of every stage checks its image before it touches a pixel: h, w in 1 .. 65535, c 1 or 3, subsampling 0 or 2,
+ *            the pixels inside src_bytes, the slot inside dst_bytes, the block count <= max_blocks.  The last stage also checks that the file
+ *            fits `capacity`.  An image that fails gets length 0, NOTHING of its slot (or outside it) is written and bit (b & 31) is OR-ed into
+ *            *bad_mask (if given; the owner zeroes it); the other images are unaffected.  A flagged image is a result, never a fault.
+ * STAGES     five launches whatever the batch holds, no read-back, no host decision, no kernel waits on another workgroup: (1) colour, padding,
+ *            downsample, DCT, quantisation -> int16 coefficients in zigzag order at the block's index in scan order, and the bit buffer
+ *            zeroed; (2) each block's code length and the prefix sum inside chunks of 256 blocks; (3) the chunk sums reduced per workgroup (the
+ *            second level, behind a launch boundary), every block's bits OR-ed in at its bit offset; (4) 0xFF bytes per 1024-byte chunk of
+ *            the packed stream; (5) header from a template, stuffed scan, EOI, length.
+ * Errors (I2I_ERR_BAD_ARG): null params; n < 0; max_blocks outside 1 .. 2^21; negative src_bytes / dst_bytes; (n > 0) src / dst / images /
+ * length / ws null, src / length / bad_mask not 4-byte aligned, images not 8-byte aligned, ws not 16-byte aligned, ws_bytes too small. */
+typedef struct {                       /* device, one per image, 48 bytes */
+    int64_t src_off;                   /* byte offset of the image's pixels in the arena */
+    int64_t dst_off;                   /* byte offset of the image's file in the output pool */
+    int32_t h, w;                      /* 1 .. 65535 */
+    int32_t c;                         /* channels of the source: 3, or 1 (replicated) */
+    int32_t quality;                   /* clamped to 1 .. 100 */
+    int32_t subsampling;               /* Pillow's numbers: 0 = 4:4:4, 2 = 4:2:0 */
+    int32_t capacity;                  /* bytes of the slot at dst_off */
+    int32_t reserved[2];               /* ignored */
+} i2i_jpeg_image;
+typedef struct {
+    const void* src; int64_t src_bytes;    /* the pixel arena (4-byte aligned) and its capacity */
+    void* dst; int64_t dst_bytes;          /* the output pool and its capacity */
+    const i2i_jpeg_image* images;      /* device [n] */
+    uint32_t* length;                  /* device [n]: bytes of every file (0: flagged) */
+    uint32_t* bad_mask;                /* optional device word */
+    void* ws; int64_t ws_bytes;        /* >= i2i_jpeg_workspace_bytes(n, max_blocks), 16-byte aligned; scratch, needs no initialisation */
+    int32_t n;
+    int32_t reserved;                  /* ignored */
+    int64_t max_blocks;                /* capacity hint, 1 .. 2^21 */
+} i2i_jpeg_encode_u8_params;
+#define I2I_JPEG_HEADER_BYTES 623
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -846,6 +910,13 @@ int i2i_tile_cut(const i2i_tile_cut_params* p, int dtype, void* stream);        
 int i2i_tile_blend_u8(const i2i_tile_blend_u8_params* p, int dtype, void* stream);     /* dtype ignored (uint8 data); one launch */
 /* The tile positions of one axis (the layout rule above i2i_tile_request): host code, returns the count or I2I_ERR_BAD_ARG. */
 int i2i_tile_positions(int L, int t, int ov, int32_t* out, int capacity);
+/* Baseline JPEG files of a ragged uint8 batch, byte-identical to Pillow's (the contract is the comment of i2i_jpeg_image); five launches. */
+int i2i_jpeg_encode_u8(const i2i_jpeg_encode_u8_params* p, int dtype, void* stream);   /* dtype ignored (uint8 data) */
+/* Bytes of the workspace for n images of at most max_blocks blocks each: host code; 0 for arguments outside the contract. */
+size_t i2i_jpeg_workspace_bytes(int n, int64_t max_blocks);
+/* The I2I_JPEG_HEADER_BYTES bytes the device writes in front of the scan, for hosts that are not Python: host code, no GPU.  subsampling 0 or
+ * 2, w and h in 1 .. 65535; returns the byte count or I2I_ERR_BAD_ARG (nothing written). */
+int i2i_jpeg_header(int quality, int subsampling, int w, int h, uint8_t* out);
 /* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
  * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
  * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
