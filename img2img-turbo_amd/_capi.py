@@ -212,6 +212,21 @@ class JpegEncodeU8Params(C.Structure):
 JPEG_HEADER_BYTES = 623
 
 
+class PngImage(C.Structure):
+    """One image of a PNG encode (i2i_png_image, 48 bytes, lives in DEVICE memory: image_ops.PNG_IMAGE_DTYPE packs it)."""
+    _fields_ = [("src_off", i64), ("dst_off", i64), ("h", i32), ("w", i32), ("c", i32), ("flags", i32), ("capacity", i32), ("reserved", i32 * 3)]
+
+
+class PngEncodeU8Params(C.Structure):
+    """i2i_png_encode_u8_params: an eager entry, not a member of i2i_op (no opcode)."""
+    _fields_ = [("src", vp), ("src_bytes", i64), ("dst", vp), ("dst_bytes", i64), ("images", vp), ("length", vp), ("bad_mask", vp), ("ws", vp),
+                ("ws_bytes", i64), ("n", i32), ("reserved", i32), ("max_bytes", i64)]
+
+
+PNG_BLOCK_BYTES = 16384
+PNG_MAX_BYTES = 1 << 27
+
+
 class NopParams(C.Structure):
     _fields_ = [("unused", i32)]
 
@@ -248,7 +263,8 @@ EXPORTS = ["i2i_abi_version", "i2i_backend", "i2i_last_error", "i2i_sizeof_op", 
            "i2i_graph_create", "i2i_graph_launch", "i2i_graph_destroy",
            "i2i_plan_load", "i2i_plan_io", "i2i_plan_write", "i2i_plan_read", "i2i_plan_ops", "i2i_plan_run", "i2i_plan_destroy",
            "i2i_plan_has_scale", "i2i_plan_set_scale", "i2i_digest", "i2i_plan_verify", "i2i_repeat",
-           "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_tile_positions", "i2i_jpeg_encode_u8", "i2i_jpeg_workspace_bytes", "i2i_jpeg_header"]
+           "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_tile_positions", "i2i_jpeg_encode_u8", "i2i_jpeg_workspace_bytes", "i2i_jpeg_header",
+           "i2i_png_encode_u8", "i2i_png_workspace_bytes", "i2i_png_bound"]
 
 
 class I2IError(RuntimeError):
@@ -302,7 +318,7 @@ class Library:
         for name in ("i2i_igemm", "i2i_gn_stats", "i2i_gn_apply", "i2i_layernorm", "i2i_softmax", "i2i_attention",
                      "i2i_nchw_to_nhwc", "i2i_nhwc_to_nchw", "i2i_posterior", "i2i_ddpm_postquant", "i2i_embed", "i2i_lora_merge", "i2i_resize_u8", "i2i_canny_u8", "i2i_randn", "i2i_twin_fold", "i2i_scan",
                      "i2i_randn_batch", "i2i_canny_u8_batch", "i2i_resize_u8_ragged", "i2i_scan_batch", "i2i_scan_verdict", "i2i_canny_auto_thr", "i2i_digest", "i2i_repeat",
-                     "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_jpeg_encode_u8"):
+                     "i2i_tile_cut", "i2i_tile_blend_u8", "i2i_jpeg_encode_u8", "i2i_png_encode_u8"):
             getattr(L, name).argtypes = [vp, C.c_int, vp]
             getattr(L, name).restype = C.c_int
         L.i2i_canny_ws_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
@@ -319,6 +335,10 @@ class Library:
         L.i2i_jpeg_workspace_bytes.restype = C.c_size_t
         L.i2i_jpeg_header.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp]
         L.i2i_jpeg_header.restype = C.c_int
+        L.i2i_png_workspace_bytes.argtypes = [C.c_int, C.c_int64]
+        L.i2i_png_workspace_bytes.restype = C.c_size_t
+        L.i2i_png_bound.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.i2i_png_bound.restype = C.c_int64
         L.i2i_lanczos_ksize.argtypes = [C.c_int, C.c_int]
         L.i2i_lanczos_ksize.restype = C.c_int
         L.i2i_lanczos_tables.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int]
@@ -398,6 +418,16 @@ class Library:
         out = (C.c_uint8 * JPEG_HEADER_BYTES)()
         self.check(min(int(self.lib.i2i_jpeg_header(int(quality), int(subsampling), int(w), int(h), C.addressof(out))), 0))
         return bytes(out)
+
+    def png_workspace_bytes(self, n, max_bytes):
+        """Bytes of the workspace i2i_png_encode_u8 needs for n images of at most ``max_bytes`` filtered bytes, h * (1 + w * c), each."""
+        return int(self.lib.i2i_png_workspace_bytes(int(n), int(max_bytes)))
+
+    def png_bound(self, w, h, c):
+        """A file size i2i_png_encode_u8 never exceeds for a w x h x c image (i2i_png_bound, host code)."""
+        n = int(self.lib.i2i_png_bound(int(w), int(h), int(c)))
+        self.check(min(n, 0))
+        return n
 
     def lanczos_tables(self, in_size, out_size, ksize_capacity=None):
         """The library's own tap tables (i2i_lanczos_tables, host code): (ksize, bounds int32 [out, 2], coeffs int32 [out, capacity]) as numpy

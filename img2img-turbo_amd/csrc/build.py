@@ -31,7 +31,7 @@ def _split(src):
     return src, [], src.replace(".hip", ".o")
 HEADERS = ["i2i_dev.h", "launch.h", os.path.join("..", "..", "include", "i2i_turbo.h")]
 # source text a single .hip file includes (not a translation unit of its own): part of that object's digest and of the library's
-INCLUDES = {"resize.hip": ["jpeg.inc"]}
+INCLUDES = {"resize.hip": ["jpeg.inc", "png.inc"]}
 LIB = os.path.join(HERE, "libi2i_turbo.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 # per-source flags.  conv3x3_w32 / gemm_w32: VALU work runs in the MFMA shadow at one wave per SIMD, where packed-f32

@@ -1060,3 +1060,5 @@ extern "C" int i2i_tile_blend_u8(const i2i_tile_blend_u8_params* p, int dtype, v
 // ------------------------------------------------------------------------------------------------------------------------
 // Baseline JPEG encoding, the last uint8 boundary op (i2i_jpeg_encode_u8, i2i_jpeg_workspace_bytes, i2i_jpeg_header)
 #include "jpeg.inc"
+// PNG encoding beside it (i2i_png_encode_u8, i2i_png_workspace_bytes, i2i_png_bound)
+#include "png.inc"

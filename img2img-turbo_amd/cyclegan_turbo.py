@@ -47,7 +47,7 @@ class CycleGAN_Turbo(TurboGeneratorBase):
 
     @torch.no_grad()
     def forward_u8(self, images_u8, *args, resize=None, resize_back=False, image_prep=None, tile=None, tile_overlap=64, tile_batch=8, jpeg=None,
-                   **kw):
+                   png=None, **kw):
         """uint8 HWC in/out on the device: ``Normalize([0.5],[0.5])(to_tensor(img))`` (src/inference_unpaired.py:47) and
         ``ToPILImage()(out*0.5+0.5)`` (:53) run inside the boundary kernels.  ``resize=(width, height)`` applies the script's
         ``transforms.Resize(..., LANCZOS)`` (:40-47, e.g. (512, 512) for "resize_512x512") before the generator and
@@ -64,7 +64,18 @@ class CycleGAN_Turbo(TurboGeneratorBase):
         requests of different sizes needs no common size.
         ``jpeg=True`` / a quality / ``(quality, "4:4:4" | "4:2:0")`` / a list of one such entry per image: the script's
         ``output_pil.save(...)`` (src/inference_unpaired.py:58) on the device, as Pix2Pix_Turbo.forward_u8 describes -- a list of ``bytes``,
-        byte-identical to Pillow's files; with ``resize_back=True`` or ``tile=`` on a list every request is encoded at its own size."""
+        byte-identical to Pillow's files; with ``resize_back=True`` or ``tile=`` on a list every request is encoded at its own size.
+        ``png=True``: the same line when the name ends in .png -- a list of ``bytes``, PNG files with Pillow's container and filtered
+        scanlines and this project's deflate stream (image_ops.png_encode_u8), lossless; composes as ``jpeg=`` does and is refused beside it."""
+        if png is not None:
+            from . import image_ops
+            want = image_ops.png_argument(png, jpeg)
+            res = self.forward_u8(images_u8, *args, resize=resize, resize_back=resize_back, image_prep=image_prep, tile=tile, tile_overlap=tile_overlap,
+                                  tile_batch=tile_batch, jpeg=jpeg, **kw)
+            if not want:
+                return res
+            with self._on_device():
+                return image_ops.png_files(res, self.lib)
         if jpeg is not None:
             from . import image_ops
             n = images_u8.shape[0] if torch.is_tensor(images_u8) else len(images_u8)

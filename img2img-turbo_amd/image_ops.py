@@ -589,6 +589,108 @@ def jpeg_files(result, spec, lib):
     return (files,) + rest if rest else files
 
 
+# ---- PNG files on the device: i2i_png_encode_u8 (include/i2i_turbo.h), six launches for any number of images of any sizes ----
+PNG_IMAGE_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("h", "<i4"), ("w", "<i4"), ("c", "<i4"), ("flags", "<i4"), ("capacity", "<i4"),
+                            ("reserved", "<i4", (3,))])
+assert PNG_IMAGE_DTYPE.itemsize == 48
+
+
+def png_stream_bytes(h, w, c):
+    """Bytes of the filtered scanline stream, h * (1 + w * c): the unit of i2i_png_encode_u8's capacity hint."""
+    return h * (1 + w * c)
+
+
+def png_encode_u8(images, *, invert=False, lib=None, capacity=None, return_tensors=False, max_bytes=None):
+    """PNG files of a batch (i2i_png_encode_u8: six launches whatever the batch holds): the container and the filtered scanline stream of
+    ``Image.fromarray(x).save(f, "PNG")``, the deflate stream this project's own (lossless either way: the files decode to the input).
+    ``images``: a uint8 [B, H, W, C] tensor or a list of uint8 [H_b, W_b, C] / [H_b, W_b] tensors of different sizes on one
+    device, C = 3 (RGB) or 1 (grey); ``invert`` (one value or one per image): 255 - x is encoded, the script's canny_viz_inv.  ``capacity``:
+    bytes reserved per file (one value or one per image; default Library.png_bound, which no file exceeds).  ``max_bytes``: the capacity
+    hint that sizes grids and workspace (default: the largest image's filtered stream; results do not depend on it).  Returns a list of
+    ``bytes`` after ONE synchronisation and ONE copy of the used bytes; an image that was flagged (its file does not fit its capacity) raises
+    I2IError naming its index.  ``return_tensors=True``: (pool uint8, offsets list, lengths int32 [B] on the device, bad_mask int32 [1])
+    without any synchronisation."""
+    lib = lib or _capi.default_library()
+    items = _request_list(images, "png_encode_u8")
+    items = [t.unsqueeze(-1) if t.dim() == 2 else t for t in items]
+    n, dev = len(items), items[0].device
+    c = int(items[0].shape[-1]) if items[0].dim() == 3 else 0
+    if c not in (1, 3) or any(t.dtype != torch.uint8 or t.dim() != 3 or t.shape[-1] != c or t.device != dev for t in items):
+        raise ValueError("png_encode_u8: uint8 [H, W, C] or [H, W] images that share the channel count (3 or 1) and the device")
+    if any(not (1 <= t.shape[0] <= 65535 and 1 <= t.shape[1] <= 65535) for t in items):
+        raise ValueError("png_encode_u8: image extents must be 1 .. 65535")
+    assert (lib.backend == "emu") == (dev.type == "cpu"), "library backend %s cannot take a tensor on %s" % (lib.backend, dev)
+    sizes = [(int(t.shape[0]), int(t.shape[1])) for t in items]
+    flags = [1 if v else 0 for v in (list(invert) if isinstance(invert, (list, tuple)) else [invert] * n)]
+    if len(flags) != n:
+        raise ValueError("png_encode_u8: %d invert flags for %d images" % (len(flags), n))
+    caps = [lib.png_bound(w, h, c) for h, w in sizes] if capacity is None else [int(v) for v in (list(capacity) if isinstance(capacity, (list, tuple)) else [capacity] * n)]
+    if len(caps) != n:
+        raise ValueError("png_encode_u8: %d capacities for %d images" % (len(caps), n))
+    largest = max(png_stream_bytes(h, w, c) for h, w in sizes)
+    max_bytes = largest if max_bytes is None else int(max_bytes)
+    if largest > _capi.PNG_MAX_BYTES:
+        raise ValueError("png_encode_u8: an image of %d filtered bytes exceeds the entry's 2^27" % largest)
+    desc = np.zeros(n, dtype=PNG_IMAGE_DTYPE)
+    src_off = dst_off = 0
+    offsets = []
+    for b, ((h, w), f, cap) in enumerate(zip(sizes, flags, caps)):
+        desc[b] = (src_off, dst_off, h, w, c, f, cap, (0, 0, 0))
+        offsets.append(dst_off)
+        src_off += _align4(h * w * c)
+        dst_off += cap
+    from . import ops as O
+    with (torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else None
+        src = _pack_arena(items)
+        desc_dev = torch.from_numpy(desc.view(np.int64).reshape(-1).copy()).to(dev)
+        pool = torch.empty(max(dst_off, 4), dtype=torch.uint8, device=dev)
+        state = torch.zeros(n + 1, dtype=torch.int32, device=dev)               # lengths [n], then the flag word
+        ws = torch.empty(max(lib.png_workspace_bytes(n, max_bytes), 16), dtype=torch.uint8, device=dev)
+        p = O.png_encode_u8(src, pool, desc_dev, state, ws, n=n, max_bytes=max_bytes, bad_mask=state[n:], dst_bytes=dst_off)
+        lib.check(lib.lib.i2i_png_encode_u8(C.addressof(p), 0, stream))
+    if return_tensors:
+        return pool, offsets, state[:n], state[n:]
+    host = state.cpu().numpy()                                                   # the one synchronisation
+    lengths = host[:n].astype(np.int64)
+    bad = [b for b in range(n) if lengths[b] == 0]
+    if bad or host[n]:
+        raise _capi.I2IError("png_encode_u8: image %d does not fit its capacity of %d bytes (or its descriptor was refused); flagged: %s"
+                             % (bad[0] if bad else -1, caps[bad[0]] if bad else 0, bad))
+    if n == 1 or int(lengths.sum()) * 2 >= dst_off:
+        used = pool[:offsets[-1] + int(lengths[-1])].cpu().numpy()
+        return [used[o:o + int(l)].tobytes() for o, l in zip(offsets, lengths)]
+    idx = torch.cat([torch.arange(o, o + int(l), device=dev) for o, l in zip(offsets, lengths)])   # the used bytes only, one copy
+    used = pool[idx].cpu().numpy()
+    ends = np.cumsum(lengths)
+    return [used[e - l:e].tobytes() for e, l in zip(ends, lengths)]
+
+
+def png_argument(png, jpeg=None):
+    """``png=`` of the models' forward_u8: None / False (off) or True; anything else, or ``png=`` beside ``jpeg=``, is refused."""
+    if png is None or png is False:
+        return False
+    if png is not True:
+        raise ValueError("png=%r: True or None (PNG has no settings here)" % (png,))
+    if jpeg is not None:
+        raise ValueError("png= and jpeg= together: one call returns one kind of file")
+    return True
+
+
+def png_files(result, lib, images=True, edges=False):
+    """What forward_u8 returned (the uint8 images, or a tuple that starts with them): with ``images`` the images are replaced by their PNG
+    files, with ``edges`` the second entry (the uint8 edge maps the generator saw) by the PNG files of the INVERTED maps, the script's
+    ``canny_viz_inv.save(..._canny.png)`` (src/inference_paired.py:48-49)."""
+    rest = ()
+    if isinstance(result, tuple):
+        result, rest = result[0], result[1:]
+    if edges:
+        rest = (png_encode_u8(rest[0], invert=True, lib=lib),) + rest[1:]
+    if images:
+        result = png_encode_u8(result, lib=lib)
+    return (result,) + rest if rest else result
+
+
 def canny_thresholds(low, high):
     """The two ints the kernels compare against: float thresholds floored (the magnitudes are integers, so ``mag > floor(t)`` is
     ``mag > t``); the kernels swap them if low > high."""

@@ -248,6 +248,20 @@ def jpeg_encode_u8(src, dst, images, length, ws, *, n, max_blocks, bad_mask=None
     return _keep(p, src, dst, images, length, ws, bad_mask)
 
 
+def png_encode_u8(src, dst, images, length, ws, *, n, max_bytes, bad_mask=None, src_bytes=None, dst_bytes=None):
+    """The params of one i2i_png_encode_u8 call (no opcode: an eager entry, ``lib.lib.i2i_png_encode_u8(addressof(p), 0, stream)``): ``src``
+    the uint8 pixel arena, ``dst`` the uint8 output pool, ``images`` a device tensor of n 48-byte i2i_png_image descriptors, ``length`` device
+    int32 / uint32 [n], ``ws`` a uint8 tensor of at least Library.png_workspace_bytes(n, max_bytes) bytes.  Everything is read at run time;
+    ``max_bytes`` sizes the grids and the workspace slots."""
+    p = K.PngEncodeU8Params()
+    p.src, p.dst, p.images, p.length, p.bad_mask, p.ws = ptr(src), ptr(dst), ptr(images), ptr(length), ptr(bad_mask), ptr(ws)
+    p.src_bytes = src.numel() * src.element_size() if src_bytes is None else int(src_bytes)
+    p.dst_bytes = dst.numel() * dst.element_size() if dst_bytes is None else int(dst_bytes)
+    p.ws_bytes = ws.numel() * ws.element_size()
+    p.n, p.max_bytes = int(n), int(max_bytes)
+    return _keep(p, src, dst, images, length, ws, bad_mask)
+
+
 def twin_fold(dst, bias, pre, cur, rg, *, bias_pre=None, bias_cur=None):
     """dst[N][K] (+ bias[N]) = the TwinConv fold of two packed layers at the device scale rg[0] (i2i_twin_fold_params).  ``pre`` / ``cur``:
     (w0 fp32 [N][K], A fp32 [rank][K] or None, B fp32 [N][rank] or None)."""

@@ -489,7 +489,7 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
 
     @torch.no_grad()
     def forward_u8(self, images_u8, *args, resize=None, sketch=False, canny=None, return_edges=False, resample="lanczos",
-                   tile=None, tile_overlap=64, tile_batch=8, jpeg=None, **kw):
+                   tile=None, tile_overlap=64, tile_batch=8, jpeg=None, png=None, **kw):
         """uint8 HWC in, uint8 HWC out ([B, H, W, 3] on the device): the callers' ``F.to_tensor`` (src/inference_paired.py:50)
         and ``ToPILImage()(out*0.5+0.5)`` (:72) run inside the boundary kernels; everything else as ``forward``.
         ``resize="multiple_of_8"`` first applies the script's ``input_image.resize((w - w % 8, h - h % 8), Image.LANCZOS)``
@@ -532,7 +532,21 @@ class Pix2Pix_Turbo(TurboGeneratorBase):
         ``output_pil.save(...)`` (src/inference_paired.py:75) on the device -- the images come back as a list of ``bytes``, each the complete
         baseline JPEG file Pillow writes for that image at that quality and subsampling, byte for byte (image_ops.jpeg_encode_u8; ``True`` is
         Pillow's default, quality 75 at 4:2:0), in the order the tensor would have had (``variations=V``: image-major, B * V files; ``tile=``
-        or a list: every request at its own size, one ragged call).  ``return_edges=True`` keeps returning the edges beside them."""
+        or a list: every request at its own size, one ragged call).  ``return_edges=True`` keeps returning the edges beside them.
+        ``png=True``: the same line when the name ends in .png, what the scripts' ``bname`` usually asks for -- a list of ``bytes``, each a
+        PNG file with Pillow's container and filtered scanlines and this project's deflate stream (image_ops.png_encode_u8; lossless: the
+        files decode to the uint8 output); composes as ``jpeg=`` does; ``png=`` beside ``jpeg=`` is a ValueError.  ``return_edges="png"``
+        (with ``canny=``): the second result is the list of PNG files of ``255 - edges``, the script's ``_canny.png`` (:48-49)."""
+        if png is not None or (isinstance(return_edges, str) and return_edges == "png"):
+            from . import image_ops
+            want = image_ops.png_argument(png, jpeg)
+            edges_png = isinstance(return_edges, str)
+            res = self.forward_u8(images_u8, *args, resize=resize, sketch=sketch, canny=canny, return_edges=bool(return_edges), resample=resample,
+                                  tile=tile, tile_overlap=tile_overlap, tile_batch=tile_batch, jpeg=jpeg, **kw)
+            if not want and not edges_png:
+                return res
+            with self._on_device():
+                return image_ops.png_files(res, self.lib, images=want, edges=edges_png)
         if jpeg is not None:
             from . import image_ops
             n = images_u8.shape[0] if torch.is_tensor(images_u8) else len(images_u8)

@@ -827,6 +827,79 @@ typedef struct {
 } i2i_jpeg_encode_u8_params;
 #define I2I_JPEG_HEADER_BYTES 623
 
+/* ---- ABI 14 addition: PNG encoding of a ragged uint8 batch on the device (i2i_png_encode_u8, i2i_png_workspace_bytes, i2i_png_bound).
+ * Purely additive like the JPEG entry -- two new structs, three new exported functions, NO opcode, i2i_op untouched, I2I_ABI_VERSION stays
+ * 14; plan files do not carry it.  A library built before the addition is recognised by the missing symbols.
+ *
+ * What output_pil.save(...) writes when the name ends in .png (src/inference_paired.py:75, src/inference_unpaired.py:58), and with
+ * flags bit 0 the script's canny_viz_inv.save(..._canny.png) (src/inference_paired.py:48-49).  PNG is lossless and the compressed bytes are
+ * not Pillow's: the CONTAINER and the FILTERED SCANLINE STREAM are Pillow's, the DEFLATE STREAM is this project's own and fully specified
+ * here (tests/png_ref.py is the integer restatement; device == oracle on whole files).  THE RULES, all integer:
+ *   container the 8-byte signature; IHDR (w, h, bit depth 8, colour type 2 for c = 3 or 0 for c = 1, 0, 0, 0); ONE IDAT; IEND; no other
+ *             chunk; a CRC-32 on every chunk.  IDAT holds 78 9C, the deflate stream and the big-endian Adler-32 of the filtered stream.
+ *   filter    Pillow's adaptive rule (ZipEncode.c, ZIP_PNG, no optimize), per row: bpp = c, the row above row 0 is zeros,
+ *             cost = sum over the filtered bytes of (v < 128 ? v : 256 - v).  Start with filter 0 (None); while the best cost is > 0 try
+ *             2 (Up), 1 (Sub), 4 (Paeth) in this order and take one only if its cost is STRICTLY smaller.  3 (Average) is never used.
+ *             Paeth: p = a + b - c; a if pa <= pb && pa <= pc, else b if pb <= pc, else c.  The filtered stream F is h rows of
+ *             S = 1 + w c bytes (the filter type, then the row).  flags bit 0: every pixel is 255 - x before filtering.
+ *   blocks    F is cut every I2I_PNG_BLOCK_BYTES = 16384 bytes; every piece is one deflate block with BTYPE = 2 and its own codes; BFINAL
+ *             on the last; zero bits up to the byte boundary behind it.  No stored block, no fixed block.
+ *   matches   position p looks at the distances 1, c, S, S - c, S + c in this order.  A distance > 32768 or > p is dropped.  The match
+ *             length is the number of k with F[p + k] == F[p + k - d] from k = 0 on, at most 258 and clipped at the end of p's block (the
+ *             source may lie in the block before).  The longest wins, ties go to the first candidate; under 3 the position is a literal.
+ *             The tokens are the greedy parse from the block's first byte: next = p + max(1, length).
+ *   lengths   for the literal/length alphabet (286 symbols, end-of-block always counted once; limit 15), the distance alphabet (30; limit
+ *             15) and the code-length alphabet (19; limit 7): the used symbols sorted ascending by (frequency, symbol); no used symbol: all
+ *             lengths 0 (a block without a match sends HDIST = 0 and one distance length of 0); one used symbol: length 1.  Otherwise
+ *             Huffman's merge over two queues (the sorted leaves, the internal nodes in the order they were made; of two equal weights the
+ *             leaf is taken first; each step takes two and appends their sum); the leaves' depths clipped at the limit and counted per
+ *             length; REPAIR while the Kraft sum exceeds 1, once per 2^-limit of excess: the largest length l < limit with a leaf loses one
+ *             leaf, l + 1 gains two, the limit row loses one; then the lengths are dealt by the sorted order, the longest to the rarest.
+ *   codes     canonical (RFC 1951 3.2.2).
+ *   header    HLIT = n_lit - 257 and HDIST = n_dist - 1 with trailing zero lengths cut (n_lit >= 257, n_dist >= 1); the n_lit + n_dist
+ *             lengths are ONE sequence, run-length coded greedily: a run of zeros emits 18 (11 .. 138) while >= 11 remain, then 17 (3 .. 10)
+ *             if >= 3 remain, then single zeros; a run of v > 0 emits v, then 16 (3 .. 6) while >= 3 remain, then single v.  HCLEN cuts
+ *             trailing zeros of the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, at least 4.
+ *   bits      LSB first; Huffman codes bit-reversed, extra bits as they are.
+ * IMAGE b    images[b] (i2i_png_image, 48 bytes, DEVICE memory): dense [h][w][c] uint8 pixels at src + src_off, c = 3 (RGB) or 1 (grey).
+ *            The file goes to dst + dst_off (any alignment), at most `capacity` bytes (i2i_png_bound(w, h, c) always suffices); length[b]
+ *            receives its size.  Sizes and flags are DEVICE STATE: one captured graph serves every set of sizes under the hint.
+ * GRID       a function of n and max_bytes only.  max_bytes, 1 .. 2^27, is the capacity hint: the largest h (1 + w c) any image will
+ *            have.  It sizes the grids and the per-image slot of the workspace (i2i_png_workspace_bytes); results do not depend on it.
+ * SAFETY     as for i2i_jpeg_image: every workgroup of every stage checks its image before it touches a pixel (h, w in 1 .. 65535, c 1 or
+ *            3, the pixels inside src_bytes, the slot inside dst_bytes, h (1 + w c) <= max_bytes); the last stage also checks that the file
+ *            fits `capacity`.  An image that fails gets length 0, NOTHING of its slot is written and bit (b & 31) is OR-ed into *bad_mask
+ *            (if given; the owner zeroes it); the other images are unaffected.  A flagged image is a result, never a fault.
+ * STAGES     SIX launches whatever the batch holds, no read-back, nothing allocated, no kernel waits on another workgroup: (1) filter rows
+ *            -> F, bit buffer zeroed; (2) the longest candidate match of every position; (3) per deflate block: greedy parse, histograms,
+ *            code lengths, codes, block header, bit offsets of its 256 segments; (4) bits in front of the block reduced per workgroup
+ *            (behind the launch boundary), tokens packed at their offsets; (5) Adler-32 and CRC-32 terms per 1024 bytes, each carried to
+ *            the end of its stream (Adler: A = A1 + A2 - 1, B = B1 + B2 + len2 (A1 - 1) mod 65521; CRC: times x^(8 len) mod the
+ *            polynomial); (6) the file and length[b].
+ * Errors (I2I_ERR_BAD_ARG): null params; n < 0; max_bytes outside 1 .. 2^27; negative src_bytes / dst_bytes; (n > 0) src / dst / images /
+ * length / ws null, length / bad_mask not 4-byte aligned, images not 8-byte aligned, ws not 16-byte aligned, ws_bytes too small. */
+typedef struct {                       /* device, one per image, 48 bytes */
+    int64_t src_off;                   /* byte offset of the image's pixels in the arena */
+    int64_t dst_off;                   /* byte offset of the image's file in the output pool */
+    int32_t h, w;                      /* 1 .. 65535 */
+    int32_t c;                         /* 3 (RGB, colour type 2) or 1 (grey, colour type 0) */
+    int32_t flags;                     /* bit 0: invert (255 - x) before filtering; other bits ignored */
+    int32_t capacity;                  /* bytes of the slot at dst_off */
+    int32_t reserved[3];               /* ignored */
+} i2i_png_image;
+typedef struct {
+    const void* src; int64_t src_bytes;    /* the pixel arena and its capacity */
+    void* dst; int64_t dst_bytes;          /* the output pool and its capacity */
+    const i2i_png_image* images;       /* device [n] */
+    uint32_t* length;                  /* device [n]: bytes of every file (0: flagged) */
+    uint32_t* bad_mask;                /* optional device word */
+    void* ws; int64_t ws_bytes;        /* >= i2i_png_workspace_bytes(n, max_bytes), 16-byte aligned; scratch, needs no initialisation */
+    int32_t n;
+    int32_t reserved;                  /* ignored */
+    int64_t max_bytes;                 /* capacity hint, 1 .. 2^27 */
+} i2i_png_encode_u8_params;
+#define I2I_PNG_BLOCK_BYTES 16384
+
 typedef struct { int32_t unused; } i2i_nop_params;
 
 typedef struct {
@@ -917,6 +990,17 @@ size_t i2i_jpeg_workspace_bytes(int n, int64_t max_blocks);
 /* The I2I_JPEG_HEADER_BYTES bytes the device writes in front of the scan, for hosts that are not Python: host code, no GPU.  subsampling 0 or
  * 2, w and h in 1 .. 65535; returns the byte count or I2I_ERR_BAD_ARG (nothing written). */
 int i2i_jpeg_header(int quality, int subsampling, int w, int h, uint8_t* out);
+/* PNG files of a ragged uint8 batch: Pillow's container and filtered stream, this project's deflate stream (the contract is the comment of
+ * i2i_png_image); six launches. */
+int i2i_png_encode_u8(const i2i_png_encode_u8_params* p, int dtype, void* stream);     /* dtype ignored (uint8 data) */
+/* Bytes of the workspace for n images of at most max_bytes filtered bytes each: host code; 0 for arguments outside the contract. */
+size_t i2i_png_workspace_bytes(int n, int64_t max_bytes);
+/* A file size the contract can never exceed: host code.  A literal costs at most 15 bits for one byte of F and a match at most
+ * 15 + 5 + 15 + 13 = 48 bits for at least three, so 16 bits per byte; a block adds 3 + 14 + 19 * 3 header bits, at most 7 bits per code
+ * length (a run symbol with its extra bits spends at most 14 bits on at least 3 lengths) for 286 + 30 lengths and 15 bits of end-of-block,
+ * 2301 bits.  With N = h (1 + w c) and K = ceil(N / 16384): 43 + ceil(2301 K / 8) + 2 N + 20.  I2I_ERR_BAD_ARG for w, h outside
+ * 1 .. 65535 or c not 1 or 3. */
+int64_t i2i_png_bound(int w, int h, int c);
 /* Pillow's LANCZOS tap tables for one axis, for hosts that are not Python: plain host code, no GPU, no allocation kept.  They restate
  * precompute_coeffs / normalize_coeffs_8bpc (src/libImaging/Resample.c) in double precision and are bit-equal to image_ops.lanczos_coeffs.
  * i2i_lanczos_ksize: taps per output coordinate, 2 * ceil(3 * max(in / out, 1)) + 1, or I2I_ERR_BAD_ARG for a size < 1.
